@@ -12,6 +12,11 @@ Arithmetic of the dense products: `value` is measured in "h2" (two fp16 pieces p
 -- the whole parity suite runs in it: tests/test_gpu_parity.py) unless TRIS_GEMM_MODE selects another; `value_x3` -- the same K
 steps in the split-bf16 x3 arithmetic of the earlier rounds, same process, same model -- is printed beside it.
 Prints ONE JSON line on rank 0.
+
+A plain run measures the headline and nothing else: set-up, one untimed priming step, W warm-up steps, the K timed steps,
+the result line.  `--full` adds the side measurements of the earlier rounds (x3 leg, live roofline of the dominant kernel
+family, input pipeline, evaluation, the other issue form, ViT-B/16, the one-rank distributed path, the CPU baseline).
+`--dump-outputs DIR` writes what the timed path computed in its last timed step as DIR/*.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -47,6 +52,9 @@ def parse():
                     "other issue form, ViT-B/16, one-rank distributed path)")
     ap.add_argument("--headline-only", action="store_true", help="profiling runs: the timed steps of `value` and nothing else "
                     "(no x3 leg, no instrumented roofline step)")
+    ap.add_argument("--full", action="store_true", help="also run the side measurements (x3 leg, roofline, pipeline, eval, "
+                    "other issue form, ViT-B/16, one-rank distributed path, CPU baseline); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/*.npy")
     return ap.parse_args()
 
 
@@ -83,6 +91,27 @@ def cpu_baseline(batches=(48, 2), timed=3):
                       f"{res[main_b]['median_s_per_step']} s/step; host has {os.cpu_count()} hw threads, {cores} used "
                       f"because more threads run slower)",
             "by_batch": {str(k): v for k, v in res.items()}}
+
+
+DUMP_SAMPLE = 1 << 22    # elements of the model-state sample written by --dump-outputs (16 MB of float32)
+
+
+def dump_outputs(path, losses, model):
+    """What a caller of the timed path receives after its last step, as .npy files under `path` (16 MB in all):
+    losses.npy        float32 [4]    (loss, l1, l4, l5) as train_step returned them
+    state_norms.npy   float64 [T]    L2 norm of every floating-point state-dict entry of the trained model, state-dict order
+    state_sample.npy  float32 [S]    a fixed sample of the same entries, flattened and concatenated in state-dict order, at the
+                                     positions torch.randint(total, (S,), generator=torch.Generator().manual_seed(0)), sorted"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    ts = [v.detach() for v in model.state_dict().values() if v.is_floating_point()]
+    np.save(os.path.join(path, "losses.npy"), losses.detach().float().cpu().numpy())
+    np.save(os.path.join(path, "state_norms.npy"), np.array([float(t.double().norm()) for t in ts], dtype=np.float64))
+    flat = torch.cat([t.reshape(-1).float() for t in ts])
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randint(flat.numel(), (min(DUMP_SAMPLE, flat.numel()),), generator=g).sort().values
+    np.save(os.path.join(path, "state_sample.npy"), flat[idx.to(flat.device)].cpu().numpy())
+    del flat
 
 
 def _mfma_peak(mode):
@@ -215,6 +244,51 @@ def main():
         comm.check_errors()    # a SyncBatchNorm mailbox exchange that timed out must fail the run, not skew it
         transport = "mailbox" if any(m is not None for m in comm.Mailbox._by_group.values()) else "torch.distributed"
 
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, losses, model)
+
+    def headline():
+        """the fields of the result line that the K timed steps above determine"""
+        dtype = {"h2": "f32 storage/accumulate; products h2 = 2 x f16 pieces", "x3": "f32 storage/accumulate; products x3 = 3 x bf16 pieces",
+                 "f32": "f32"}[mode]
+        return {"metric": f"Stage-1 training images/sec @320px bs48 (TRIS {a.backbone}, 3 negatives)",
+                "value": round(world * a.batch * a.steps / dt, 2), "unit": "img/s", "n_gpus": world, "steps": a.steps,
+                "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": dtype, "gemm_mode": mode, "data": "synthetic",
+                "config": {"workload": "Stage-1 train step, RefCOCOg-shaped synthetic batch: 48 img/GPU 320x320, "
+                                       f"20-token query + 3 negative queries per image, {a.backbone} trunk + frozen aux "
+                                       "CLIP ViT-B/32, AdamW (BASELINE.json " +
+                                       ("configs[2]/[3])" if a.backbone == "clip-RN50" else
+                                        "configs[4]; the reference defines no such model: parity unpinned, DESIGN.md)"),
+                           "per_gpu_batch": a.batch, "global_batch": world * a.batch, "size": 320, "query_len": QL,
+                           "negative_samples": 3, "parallelism": f"dp{world}", "sync_bn": world > 1, "sync_bn_transport": transport},
+                "untimed_priming_steps": 1, "losses_last_step": [round(v, 5) for v in loss_vals],
+                "host_issue_ms_per_step": round(host_issue / a.steps * 1e3, 3),
+                "comm_exposed_ms": None if comm_exposed is None else round(comm_exposed, 3),
+                "sparse_embed_exchange": bool(reducer is not None and reducer.sparse_embed),
+                "streams": {"text_encoders_on_side_stream": cfg.text_stream, "weight_gradients_on_side_stream": cfg.wgrad_stream,
+                            "compute_on_own_stream": bool(cfg.own_stream and world == 1)},
+                "h2_operand_planes": bool(cfg.h2_planes and mode == "h2"),
+                "h2_out_of_range_operands": None if h2_range is None else h2_range["out_of_range_operands"], "h2_range": h2_range,
+                "step_issue": {"0": "eager launches", "1": "one hipGraph", "seg": "chain of single-stream hipGraphs"}[cfg.step_graph],
+                "rccl": rccl,    # (N > 1: what the collective backend saw -- N ranks on N distinct devices, asserted at start-up)
+                "full": a.full}
+
+    def finish(out):
+        if world > 1:
+            dist.barrier()
+            __import__('tris_amd.comm', fromlist=['x']).shutdown()
+            dist.destroy_process_group()
+        if rank == 0:
+            line = json.dumps(out)
+            sys.stderr.flush()
+            try:   # RCCL prints a version banner through C stdio (buffered when stdout is a pipe): push it out BEFORE the JSON
+                import ctypes
+                ctypes.CDLL(None).fflush(None)
+            except Exception:
+                pass
+            print(line, flush=True)  # the ONE JSON line, last thing this process writes
+
     # ---- the same K steps in the x3 arithmetic of the earlier rounds: same process, same model, same timing rule ----------------
     value_x3 = None
     if a.headline_only:
@@ -225,6 +299,9 @@ def main():
             dist.barrier()
             __import__('tris_amd.comm', fromlist=['x']).shutdown()
             dist.destroy_process_group()
+        return
+    if not a.full:     # a plain run: the headline and nothing else
+        finish(headline() if rank == 0 else None)
         return
     if mode == "h2":
         ops.set_gemm_mode("x3")
@@ -387,30 +464,9 @@ def main():
             pass
     out = None
     if rank == 0:
-        dtype = {"h2": "f32 storage/accumulate; products h2 = 2 x f16 pieces", "x3": "f32 storage/accumulate; products x3 = 3 x bf16 pieces",
-                 "f32": "f32"}[mode]
-        out = {"metric": f"Stage-1 training images/sec @320px bs48 (TRIS {a.backbone}, 3 negatives)",
-               "value": round(world * a.batch * a.steps / dt, 2), "unit": "img/s", "n_gpus": world, "steps": a.steps,
-               "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
-               "scaling": "weak", "vs_baseline": None, "dtype": dtype, "gemm_mode": mode, "data": "synthetic",
-               "config": {"workload": "Stage-1 train step, RefCOCOg-shaped synthetic batch: 48 img/GPU 320x320, "
-                                      f"20-token query + 3 negative queries per image, {a.backbone} trunk + frozen aux "
-                                      "CLIP ViT-B/32, AdamW (BASELINE.json " +
-                                      ("configs[2]/[3])" if a.backbone == "clip-RN50" else
-                                       "configs[4]; the reference defines no such model: parity unpinned, DESIGN.md)"),
-                          "per_gpu_batch": a.batch, "global_batch": world * a.batch, "size": 320, "query_len": QL,
-                          "negative_samples": 3, "parallelism": f"dp{world}", "sync_bn": world > 1, "sync_bn_transport": transport},
-               "untimed_priming_steps": 1, "losses_last_step": [round(v, 5) for v in loss_vals], "ms_single_step_synced": round(one, 3),
-               "host_issue_ms_per_step": round(host_issue / a.steps * 1e3, 3),
-               "comm_exposed_ms": None if comm_exposed is None else round(comm_exposed, 3),
-               "sparse_embed_exchange": bool(reducer is not None and reducer.sparse_embed),
-               "streams": {"text_encoders_on_side_stream": cfg.text_stream, "weight_gradients_on_side_stream": cfg.wgrad_stream,
-                           "compute_on_own_stream": bool(cfg.own_stream and world == 1)},
-               "h2_operand_planes": bool(cfg.h2_planes and mode == "h2"),
-               "h2_out_of_range_operands": None if h2_range is None else h2_range["out_of_range_operands"], "h2_range": h2_range,
-               "step_issue": {"0": "eager launches", "1": "one hipGraph", "seg": "chain of single-stream hipGraphs"}[cfg.step_graph],
-               "rccl": rccl,    # (N > 1: what the collective backend saw -- N ranks on N distinct devices, asserted at start-up)
-               "roofline": roof, "roofline_xattn": roof_x, "roofline_xattn_bwd": roof_xb}
+        out = headline()
+        out.update({"ms_single_step_synced": round(one, 3), "roofline": roof, "roofline_xattn": roof_x,
+                    "roofline_xattn_bwd": roof_xb})
         if value_x3 is not None:
             out["value_x3"] = value_x3["value"]
             out["x3"] = dict(value_x3, note="the same K steps in the split-bf16 x3 arithmetic (the arithmetic of `value` in rounds 1-3), "
@@ -499,20 +555,7 @@ def main():
                 out["dist_path_one_rank"] = {"error": repr(e)}
         if not a.no_cpu_baseline and a.backbone == "clip-RN50":
             out["cpu_baseline"] = cpu_baseline(tuple(int(x) for x in a.cpu_batches.split(",")))
-    if world > 1:
-        dist.barrier()
-        __import__('tris_amd.comm', fromlist=['x']).shutdown()
-        dist.destroy_process_group()
-    if rank == 0:
-        line = json.dumps(out)
-        sys.stderr.flush()
-        try:   # RCCL prints a version banner through C stdio (buffered when stdout is a pipe): push it out BEFORE the JSON
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-        print(line, flush=True)  # the ONE JSON line, last thing this process writes
-
+    finish(out)
 
 if __name__ == "__main__":
     main()

@@ -1,5 +1,5 @@
 """Input pipeline, host side: Pillow-exact resize tables, COCO mask restatement, REFER index /
-ReferDataset sampling semantics against the reference-generated fixture g9 and (where mounted) the live reference."""
+ReferDataset sampling semantics against the reference-generated fixtures g9 and g12."""
 import hashlib
 import os
 
@@ -137,29 +137,36 @@ def test_refer_index_queries(mini):
         REFER(root, "nosuchset", "umd")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference tree not mounted on this machine")
-def test_refer_dataset_matches_live_reference(tmp_path):
-    from oracle import ref_shim
-    RefDS, ref_tf = ref_shim.install_dataset()
+def test_refer_dataset_matches_live_reference(tmp_path, golden):
+    """every item of three configurations against what the reference's ReferDataset returned for them (real BPE tokenizer,
+    recorded by oracle/gen_golden_live.py: tests/golden/g12_reference_dataset.npz)"""
+    import json
+    ref = golden("g12_reference_dataset.npz")
     root = make_mini_refer(str(tmp_path), n_images=9, seed=23)
-    for split, ev, neg in (("train", False, 2), ("val", True, 0), ("train", False, 0)):
+    for c, (split, ev, neg) in enumerate((("train", False, 2), ("val", True, 0), ("train", False, 0))):
         kw = dict(refer_data_root=root, dataset="refcocog", splitBy="umd", split=split, size=40, max_tokens=20,
                   eval_mode=ev, negative_samples=neg)
-        a = RefDS(image_transforms=ref_tf(40, train=not ev), **kw)          # real BPE tokenizer on both sides
         b = ReferDataset(image_transforms=get_transform(40, train=not ev), **kw)
-        assert len(a) == len(b) and a.ref_ids == b.ref_ids
-        np.random.seed(3)
-        ra = [a[i] for i in range(len(a))]
+        assert list(b.ref_ids) == ref[f"ds{c}_ref_ids"].tolist()
         np.random.seed(3)
         rb = [b[i] for i in range(len(b))]
-        for (sa, ta), (sb, tb) in zip(ra, rb):
-            assert sa.keys() == sb.keys() and ta.keys() == tb.keys()
-            for k in sa:
-                assert torch.equal(sa[k], sb[k]) and sa[k].dtype == sb[k].dtype if torch.is_tensor(sa[k]) else sa[k] == sb[k], k
-            for k in ta:
-                if torch.is_tensor(ta[k]):
-                    assert torch.equal(ta[k], tb[k]) and ta[k].dtype == tb[k].dtype, k
-                elif isinstance(ta[k], np.ndarray):
-                    assert np.array_equal(ta[k], tb[k]) and ta[k].dtype == tb[k].dtype, k
-                else:
-                    assert ta[k] == tb[k], k
+        keys = {k[len(f"ds{c}_"):] for k in ref.files if k.startswith(f"ds{c}_") and k != f"ds{c}_ref_ids"}
+        assert keys == {f"{i}_{p}_{k}" + ("" if torch.is_tensor(v) or isinstance(v, np.ndarray) else "__json")
+                        for i, item in enumerate(rb) for p, d in zip("st", item) for k, v in d.items()}
+        for i, item in enumerate(rb):
+            for p, d in zip("st", item):
+                for k, v in d.items():
+                    key = f"ds{c}_{i}_{p}_{k}"
+                    if torch.is_tensor(v):
+                        want = torch.from_numpy(ref[key])
+                        assert torch.equal(v, want) and v.dtype == want.dtype, key
+                    elif isinstance(v, np.ndarray):
+                        assert np.array_equal(v, ref[key]) and v.dtype == ref[key].dtype, key
+                    else:
+                        assert json.loads(str(ref[key + "__json"])) == _jsonable(v), key
+
+
+def _jsonable(v):
+    if isinstance(v, (list, tuple)):
+        return [_jsonable(x) for x in v]
+    return v.item() if isinstance(v, np.generic) else v

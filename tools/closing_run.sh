@@ -1,10 +1,11 @@
 # closing run of a round (on the GPU box: gpurun -- bash tools/closing_run.sh): full GPU test suite, smoke, bench (with CPU baseline and every side leg; autotuner log per arithmetic), the cross-attention phase table, then the profile sets of tools/closing_profiles.sh for h2 and x3; outputs under gpurun_out/, copied to profiles/ by hand
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 export TAG=${TAG:-r6}
-timeout 1800 python -m pytest tests -x -q -m gpu -p no:cacheprovider > gpurun_out/${TAG}_gputests.log 2>&1 < /dev/null; echo "tests rc=$?"; grep -E "passed|failed" gpurun_out/${TAG}_gputests.log | tail -2
-timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/${TAG}_smoke.log 2>&1 < /dev/null; tail -1 gpurun_out/${TAG}_smoke.log
-TRIS_TUNE_LOG=gpurun_out/${TAG}_autotune_log_all.txt timeout 1200 python bench.py > gpurun_out/${TAG}_bench.log 2>&1 < /dev/null; grep "^{" gpurun_out/${TAG}_bench.log > gpurun_out/${TAG}_bench.json; cut -c1-300 gpurun_out/${TAG}_bench.json
-grep -E "mode=3|mode=4" gpurun_out/${TAG}_autotune_log_all.txt > gpurun_out/${TAG}_autotune_log_h2.txt; grep "mode=1" gpurun_out/${TAG}_autotune_log_all.txt > gpurun_out/${TAG}_autotune_log_x3.txt; wc -l gpurun_out/${TAG}_autotune_log_*.txt | tail -3
+OUT=${OUT:-results}; mkdir -p "$OUT"   # logs of the suite, smoke() and the full benchmark run below
+timeout 1800 python -m pytest tests -x -q -m gpu -p no:cacheprovider > $OUT/${TAG}_gputests.log 2>&1 < /dev/null; echo "tests rc=$?"; grep -E "passed|failed" $OUT/${TAG}_gputests.log | tail -2
+timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/${TAG}_smoke.log 2>&1 < /dev/null; tail -1 $OUT/${TAG}_smoke.log
+TRIS_TUNE_LOG=$OUT/${TAG}_autotune_log_all.txt timeout 1200 python bench.py --full > $OUT/${TAG}_bench.log 2>&1 < /dev/null; grep "^{" $OUT/${TAG}_bench.log > $OUT/${TAG}_bench.json; cut -c1-300 $OUT/${TAG}_bench.json
+grep -E "mode=3|mode=4" $OUT/${TAG}_autotune_log_all.txt > $OUT/${TAG}_autotune_log_h2.txt; grep "mode=1" $OUT/${TAG}_autotune_log_all.txt > $OUT/${TAG}_autotune_log_x3.txt; wc -l $OUT/${TAG}_autotune_log_*.txt | tail -3
 timeout 300 python tools/xattn_px_trace.py > gpurun_out/${TAG}_xattn_phase_trace.txt 2>&1 < /dev/null; tail -18 gpurun_out/${TAG}_xattn_phase_trace.txt | cut -c1-200
 timeout 300 python tools/xattn_check.py > gpurun_out/${TAG}_xattn_forms.txt 2>&1 < /dev/null; tail -3 gpurun_out/${TAG}_xattn_forms.txt | cut -c1-200
 bash tools/xattn_pmc.sh ${TAG} > /dev/null 2>&1 < /dev/null; cut -c1-160 gpurun_out/${TAG}_xattn_pmc.txt
