@@ -562,6 +562,56 @@ int tris_mbox_bn_bwd_exchange_f32(const float* sum_dz, const float* sum_dzx, int
                                   unsigned* seq, int cap_floats, long spin_limit, int* err, const float* gamma, const float* invstd,
                                   float inv_count, float xhat_max, const unsigned* dz_word, unsigned* bound_word, void* stream);
 
+/* ---- Stage-2 decoder (csrc/seg.hip; model/model_stage2.py, train_stage2.py) -------------------------------------------
+ * Channels-last activations [M = B*h*w, C].  Every sum is a fixed-order two-stage reduction (fp64 partials), no atomics.  Scalars
+ * that training changes (the PReLU slope, the loss gradients) are DEVICE pointers. */
+/* workspace of tris_bn_prelu_bwd_reduce_f32 / tris_head1_bwd_f32 (bytes, >= what either needs for M rows of C channels) */
+long tris_seg_workspace_bytes(long M, int C);
+/* ConvBNRelu's BatchNorm2d + nn.PReLU() with ONE slope (model_stage2.py:11-27): z = (X - mean) * invstd * gamma + beta (the
+ * expression of tris_bn_apply_f32), Y = z > 0 ? z : slope[0] * z.  Train mode: mean / invstd from tris_bn_finalize_f32 or
+ * tris_bn_stats_f32; eval mode: running statistics.  C % 4 == 0. */
+int tris_bn_prelu_fwd_f32(const float* X, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                          const float* slope, float* Y, long M, int C, void* stream);
+/* backward reduce: z recomputed from X; dz = dY * (z > 0 ? 1 : slope); sum_dz[C] (= dbeta), sum_dzx[C] = sum dz * xhat (= dgamma),
+ * *dslope = sum dY * z [z <= 0] over all channels.  1024 % C == 0.  workspace: tris_seg_workspace_bytes(M, C). */
+int tris_bn_prelu_bwd_reduce_f32(const float* dY, const float* X, const float* mean, const float* invstd, const float* gamma,
+                                 const float* beta, const float* slope, long M, int C, float* sum_dz, float* sum_dzx, float* dslope,
+                                 double* workspace, void* stream);
+/* backward apply: dX = gamma invstd (dz - sum_dz inv_count - xhat sum_dzx inv_count) (tris_bn_bwd_apply_f32's expression); eval
+ * mode: inv_count = 0 (the statistics are constants) */
+int tris_bn_prelu_bwd_apply_f32(const float* dY, const float* X, const float* mean, const float* invstd, const float* gamma,
+                                const float* beta, const float* slope, const float* sum_dz, const float* sum_dzx, float inv_count,
+                                float* dX, long M, int C, void* stream);
+/* Upsample (F.interpolate bilinear, align_corners=False, model_stage2.py:29-35) of X [B,Hi,Wi,C] to [B,Ho,Wo,C] with the skip add
+ * of the top-down path (:127-129 `Upsample(output_k(.), size) + dem`): up <- the upsampled map, sum <- up + skip (either output may
+ * be NULL; skip and sum go together).  Source indices and the blend are tris_resize_bilinear_fwd_f32's, so the NCHW and NHWC
+ * results agree bit for bit.  backward (gather form, any Ho >= Hi, Wo >= Wi): dX = sum over the output window of (d_up + d_sum)
+ * (either may be NULL); the skip's gradient is d_sum itself.  C % 4 == 0. */
+int tris_upsample_nhwc_fwd_f32(const float* X, const float* skip, float* up, float* sum, int B, int Hi, int Wi, int Ho, int Wo,
+                               int C, void* stream);
+int tris_upsample_nhwc_bwd_f32(const float* d_up, const float* d_sum, float* dX, int B, int Hi, int Wi, int Ho, int Wo, int C,
+                               void* stream);
+/* the one-channel head nn.Conv2d(C, 1, 1, bias=False) of final_seg1..4 (model_stage2.py:75-86): Y[m] = sum_c X[m,c] w[c];
+ * backward dX = g (x) w, dw = sum_m g[m] X[m,:].  C % 32 == 0, 1024 % C == 0.  workspace: tris_seg_workspace_bytes(M, C). */
+int tris_head1_fwd_f32(const float* X, const float* w, float* Y, long M, int C, void* stream);
+int tris_head1_bwd_f32(const float* g, const float* X, const float* w, float* dX, float* dw, long M, int C, double* workspace,
+                       void* stream);
+/* criterion = F.binary_cross_entropy_with_logits(out, target.float(), reduction='mean') for the four heads (model_stage2.py:139-141,
+ * train_stage2.py:314-319): target int64 (target_f32 = 0, the pseudo masks read as is) or fp32 (target_f32 = 1); element loss
+ * max(x,0) - x t + log1p(exp(-|x|)), fp64 partials; losses[5] = {l1 + l2 + l3 + l4, l1, l2, l3, l4}.  x2..x4 may be NULL (absent
+ * heads: loss 0, no work).  backward: g = DEVICE gradient of losses[5]; dx_k = (sigmoid(x) - t)(g[0] + g[k+1]) / n.  workspace:
+ * tris_bce4_workspace_bytes(n). */
+long tris_bce4_workspace_bytes(long n);
+int tris_bce4_fwd_f32(const float* x1, const float* x2, const float* x3, const float* x4, const void* target, int target_f32, long n,
+                      float* losses, double* workspace, void* stream);
+int tris_bce4_bwd_f32(const float* x1, const float* x2, const float* x3, const float* x4, const void* target, int target_f32,
+                      const float* g, float* d1, float* d2, float* d3, float* d4, long n, void* stream);
+/* Evaluation of a SIGNED map (Stage-2 logits; validate.py:179-191 as written): cam = bilinear(align_corners=True) / (max + 1e-5)
+ * whatever the sign of the max (a negative max flips the sign), mask = cam > 1e-9, out_iu = {I, U, first arg-max of cam}.
+ * tris_eval_post_f32 (the arg-max of the raw map) stays the Stage-1 entry.  map: S x S.  workspace >= 2049 + 4*1024 floats. */
+int tris_eval_post_signed_f32(const float* map, int S, const unsigned char* target, int oH, int oW, float* cam, long* out_iu,
+                              float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,68 @@
+// Bilinear source-index arithmetic shared by every resize of the library: the NCHW resize and the response maps
+// (heads.hip), the evaluation post-processing (eval.hip) and the channels-last decoder upsample (seg.hip).  One copy of
+// the expressions, so the layouts agree bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace {
+
+// PyTorch source-index conventions (upsample_bilinear2d): align_corners=False: src = (dst+0.5)*in/out-0.5 clamped
+// at 0; True: src = dst*(in-1)/(out-1).
+struct Lerp { int i0, i1; float w1; };
+__device__ __forceinline__ Lerp lerp_of(int dst, int in, int out, int align) {
+  float src;
+  if (align) {
+    float sc = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
+    src = sc * (float)dst;
+  } else {
+    float sc = (float)in / (float)out;
+    src = sc * ((float)dst + 0.5f) - 0.5f;
+    if (src < 0.f) src = 0.f;
+  }
+  Lerp l;
+  l.i0 = (int)src;
+  if (l.i0 > in - 1) l.i0 = in - 1;
+  l.i1 = l.i0 + (l.i0 < in - 1 ? 1 : 0);
+  l.w1 = src - (float)l.i0;
+  return l;
+}
+// weight with which input index `y` contributes to output index `dst`
+__device__ __forceinline__ float contrib(int dst, int in, int out, int align, int y) {
+  Lerp l = lerp_of(dst, in, out, align);
+  float w = 0.f;
+  if (l.i0 == y) w += 1.0f - l.w1;
+  if (l.i1 == y) w += l.w1;
+  return w;
+}
+// conservative output window [lo, hi] that can reference input index y
+__device__ __forceinline__ void window(int y, int in, int out, int align, int& lo, int& hi) {
+  if (in == 1) { lo = 0; hi = out - 1; return; }
+  float a, b;
+  if (align) {
+    float inv = out > 1 ? (float)(out - 1) / (float)(in - 1) : 0.f;
+    a = ((float)y - 1.f) * inv;
+    b = ((float)y + 1.f) * inv;
+  } else {
+    float r = (float)out / (float)in;
+    a = ((float)y - 0.5f) * r - 0.5f;
+    b = ((float)y + 1.5f) * r - 0.5f;
+  }
+  lo = (int)floorf(a) - 1;
+  hi = (int)ceilf(b) + 1;
+  if (y == 0 || lo < 0) lo = 0;
+  if (y == in - 1 || hi > out - 1) hi = out - 1;
+}
+
+// align_corners=True sample of an SxS map at output pixel (oy, ox) of an oH x oW grid (validate.py:180)
+__device__ __forceinline__ float sample_ac(const float* __restrict__ m, int S, int oH, int oW, int oy, int ox) {
+  float sy = oH > 1 ? (float)(S - 1) / (float)(oH - 1) : 0.f, sx = oW > 1 ? (float)(S - 1) / (float)(oW - 1) : 0.f;
+  float fy = sy * (float)oy, fx = sx * (float)ox;
+  int y0 = min((int)fy, S - 1), x0 = min((int)fx, S - 1);
+  int y1 = y0 + (y0 < S - 1 ? 1 : 0), x1 = x0 + (x0 < S - 1 ? 1 : 0);
+  float wy = fy - (float)y0, wx = fx - (float)x0;
+  float v00 = m[y0 * S + x0], v01 = m[y0 * S + x1], v10 = m[y1 * S + x0], v11 = m[y1 * S + x1];
+  float top = v00 + wx * (v01 - v00), bot = v10 + wx * (v11 - v10);
+  return top + wy * (bot - top);
+}
+
+}  // namespace

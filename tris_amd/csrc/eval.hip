@@ -3,19 +3,9 @@
 // and the arg-max pixel for the pointing-game hit test.  Integer counts are exact (64-bit atomics).
 #include "common.h"
 #include "tris_hip.h"
+#include "bilinear.h"
 
 namespace {
-__device__ __forceinline__ float sample_ac(const float* __restrict__ m, int S, int oH, int oW, int oy, int ox) {
-  float sy = oH > 1 ? (float)(S - 1) / (float)(oH - 1) : 0.f, sx = oW > 1 ? (float)(S - 1) / (float)(oW - 1) : 0.f;
-  float fy = sy * (float)oy, fx = sx * (float)ox;
-  int y0 = min((int)fy, S - 1), x0 = min((int)fx, S - 1);
-  int y1 = y0 + (y0 < S - 1 ? 1 : 0), x1 = x0 + (x0 < S - 1 ? 1 : 0);
-  float wy = fy - (float)y0, wx = fx - (float)x0;
-  float v00 = m[y0 * S + x0], v01 = m[y0 * S + x1], v10 = m[y1 * S + x0], v11 = m[y1 * S + x1];
-  float top = v00 + wx * (v01 - v00), bot = v10 + wx * (v11 - v10);
-  return top + wy * (bot - top);
-}
-
 // pass 1: per-block (max, first arg-max) partials -> ws[2*blk], ws[2*blk+1] (index stored as float bits)
 __global__ __launch_bounds__(256) void eval_max_kernel(const float* __restrict__ m, int S, int oH, int oW,
                                                        float* __restrict__ ws) {

@@ -4,6 +4,7 @@
 // All tiny, latency/HBM-bound: one workgroup per image / row group, wavefront shuffles for the row reductions.
 #include "common.h"
 #include "tris_hip.h"
+#include "bilinear.h"
 
 namespace {
 
@@ -178,53 +179,7 @@ __global__ __launch_bounds__(256) void cls_head_bwd_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------------ bilinear
-// PyTorch source-index conventions (upsample_bilinear2d): align_corners=False: src = (dst+0.5)*in/out-0.5 clamped
-// at 0; True: src = dst*(in-1)/(out-1).
-struct Lerp { int i0, i1; float w1; };
-__device__ __forceinline__ Lerp lerp_of(int dst, int in, int out, int align) {
-  float src;
-  if (align) {
-    float sc = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-    src = sc * (float)dst;
-  } else {
-    float sc = (float)in / (float)out;
-    src = sc * ((float)dst + 0.5f) - 0.5f;
-    if (src < 0.f) src = 0.f;
-  }
-  Lerp l;
-  l.i0 = (int)src;
-  if (l.i0 > in - 1) l.i0 = in - 1;
-  l.i1 = l.i0 + (l.i0 < in - 1 ? 1 : 0);
-  l.w1 = src - (float)l.i0;
-  return l;
-}
-// weight with which input index `y` contributes to output index `dst`
-__device__ __forceinline__ float contrib(int dst, int in, int out, int align, int y) {
-  Lerp l = lerp_of(dst, in, out, align);
-  float w = 0.f;
-  if (l.i0 == y) w += 1.0f - l.w1;
-  if (l.i1 == y) w += l.w1;
-  return w;
-}
-// conservative output window [lo, hi] that can reference input index y
-__device__ __forceinline__ void window(int y, int in, int out, int align, int& lo, int& hi) {
-  if (in == 1) { lo = 0; hi = out - 1; return; }
-  float a, b;
-  if (align) {
-    float inv = out > 1 ? (float)(out - 1) / (float)(in - 1) : 0.f;
-    a = ((float)y - 1.f) * inv;
-    b = ((float)y + 1.f) * inv;
-  } else {
-    float r = (float)out / (float)in;
-    a = ((float)y - 0.5f) * r - 0.5f;
-    b = ((float)y + 1.5f) * r - 0.5f;
-  }
-  lo = (int)floorf(a) - 1;
-  hi = (int)ceilf(b) + 1;
-  if (y == 0 || lo < 0) lo = 0;
-  if (y == in - 1 || hi > out - 1) hi = out - 1;
-}
-
+// (source-index arithmetic: bilinear.h, shared with the channels-last resize of csrc/seg.hip)
 __global__ void resize_fwd_kernel(const float* __restrict__ X, float* __restrict__ Y, int planes, int Hi, int Wi, int Ho,
                                   int Wo, int align) {
   long n = (long)planes * Ho * Wo;

@@ -29,9 +29,7 @@ class ReferDataset(data.Dataset):
         self.refer = REFER(refer_data_root, dataset, splitBy)
         self.scales = scales
         self.size = size
-        self.pseudo_path = pseudo_path
-        if pseudo_path is not None:
-            raise NotImplementedError("pseudo_path feeds Stage-2 training, outside the Stage-1 path (SURVEY.md 8f)")
+        self.pseudo_path = pseudo_path   # Stage-2 training: the directory of IRNet's pseudo masks (load_pseudo)
         self.max_tokens = max_tokens
         self.ref_ids = self.refer.getRefIds(split=split)
         self.imgs = [self.refer.Imgs[i] for i in self.refer.getImgIds(self.ref_ids)]
@@ -78,6 +76,16 @@ class ReferDataset(data.Dataset):
     def load_pil(self, index):
         """-> (RGB PIL image, mask, bbox)"""
         return (self.load_image(index),) + self.load_mask(index)
+
+    def load_pseudo(self, index):
+        """Stage-2 target of a training item (ReferDataset.py:178-186): `{index}_{img_id}.npy` holds a pickled dict whose 'mask'
+        [K,h,w] are the ref's instance masks; their SUM (overlaps count twice) as an 'F' image, NEAREST-resized to size x size
+        -> int64 [1,S,S].  No random draw: the call order of sample_text is unchanged."""
+        _, img_id, _ = self.image_record(index)
+        info = np.load(os.path.join(self.pseudo_path, f"{index}_{img_id}.npy"), allow_pickle=True).item()
+        gt = (info["mask"] * 1.0).sum(0)
+        gt = Image.fromarray(gt).resize((self.size, self.size), Image.NEAREST)   # (F.resize of a PIL image, (h, w) -> (w, h))
+        return torch.tensor(np.asarray(gt), dtype=torch.int64).unsqueeze(0)
 
     # ---- text side (all the randomness of a sample, in the reference's call order) ---------------------------------
     def negative_pool(self, index):
@@ -129,6 +137,7 @@ class ReferDataset(data.Dataset):
             samples["word_masks"] = torch.cat([a.unsqueeze(-1) for a in self.word_masks[index]], dim=-1)
             sentences = list(self.all_sentences[index])
             neg = None
+            pseudo_gt = None
         else:
             pick = self.sample_text(index)
             c = pick["choice"]
@@ -136,6 +145,7 @@ class ReferDataset(data.Dataset):
             samples["word_masks"] = self.word_masks[index][c]
             sentences = self.all_sentences[index][c]
             neg = pick["neg"]
+            pseudo_gt = self.load_pseudo(index) if self.pseudo_path is not None else None
         if self.negative_samples > 0:
             # (in eval mode the reference would hit an unbound name here; evaluation always runs with 0 negatives)
             samples["neg_sents"] = [self.all_sentences[j][s] for j, s in neg]
@@ -148,4 +158,6 @@ class ReferDataset(data.Dataset):
             "orig_size": np.array([h, w]),
             "img_path_full": rec["file_name"],
         }
+        if pseudo_gt is not None:
+            targets["pseudo_gt"] = pseudo_gt
         return samples, targets

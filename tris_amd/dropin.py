@@ -31,6 +31,7 @@ import sys
 ALIASES = {
     "model": "tris_amd.model",
     "model.model_stage1": "tris_amd.model.model_stage1",
+    "model.model_stage2": "tris_amd.model.model_stage2",
     "model.attn": "tris_amd.model.attn",
     "model.utils": "tris_amd.model.utils",
     "CLIP": "tris_amd.CLIP",
@@ -49,6 +50,7 @@ ALIASES = {
     "dataset.transform": "tris_amd.dataset.transform",
     "dataset.refer": "tris_amd.dataset.refer",
     "train_stage1": "tris_amd.train_stage1",
+    "train_stage2": "tris_amd.train_stage2",
 }
 
 _installed = {}

@@ -2925,3 +2925,192 @@ def gather_rows(table, index):
     if index.numel():
         call("tris_gather_rows", P(table), P(index), index.numel(), row_bytes, P(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------------ Stage-2 decoder
+# (csrc/seg.hip; reference model/model_stage2.py, train_stage2.py)  Activations channels-last [B,h,w,C] as everywhere else.
+class BnPreluFn(torch.autograd.Function):
+    """BatchNorm2d + nn.PReLU() (one slope) on channels-last x [..., C]: ConvBNRelu's tail (model_stage2.py:22-27).  Train mode: batch
+    statistics from the producing conv's epilogue (x._bn_part) or a statistics pass, running statistics updated like torch's."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, rmean, rvar, slope, training, momentum, eps):
+        _chk(x, gamma, beta, rmean, rvar, slope)
+        part = getattr(x, "_bn_part", None) if training else None
+        x = unplanes(x).contiguous()
+        C = x.shape[-1]
+        M = x.numel() // C
+        if training:
+            stats = torch.empty(3 * C, device=x.device, dtype=torch.float32)
+            if part is not None:
+                call("tris_bn_finalize_f32", part[0].data_ptr(), part[1], M, C, eps, momentum, P(stats), P(rmean), P(rvar), _stream())
+            else:
+                ws = workspace(query("tris_col_workspace_bytes", M, C))
+                call("tris_bn_stats_f32", P(x), M, C, eps, momentum, P(stats), P(rmean), P(rvar), P(ws), _stream())
+            mean, invstd = stats[:C], stats[C:2 * C]
+        else:
+            mean, invstd = rmean, torch.rsqrt(rvar + eps)
+        y = torch.empty_like(x)
+        call("tris_bn_prelu_fwd_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(slope), P(y), M, C, _stream())
+        ctx.cfg = (M, C, bool(training))
+        ctx.params = (gamma, beta, slope)
+        ctx.save_for_backward(x, gamma, beta, mean, invstd, slope)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, beta, mean, invstd, slope = ctx.saved_tensors
+        M, C, training = ctx.cfg
+        dy = unplanes(pl_grad_in(dy.contiguous()))
+        sums = torch.empty(2 * C + 1, device=x.device, dtype=torch.float32)
+        ws = workspace(query("tris_seg_workspace_bytes", M, C))
+        call("tris_bn_prelu_bwd_reduce_f32", P(dy), P(x), P(mean), P(invstd), P(gamma), P(beta), P(slope), M, C, P(sums),
+             P(sums, C), P(sums, 2 * C), P(ws), _stream())
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            # eval mode: the statistics are constants, so the mean terms drop out (inv_count 0)
+            call("tris_bn_prelu_bwd_apply_f32", P(dy), P(x), P(mean), P(invstd), P(gamma), P(beta), P(slope), P(sums), P(sums, C),
+                 1.0 / float(M) if training else 0.0, P(dx), M, C, _stream())
+        g, b, a = ctx.params
+        dg = _emit(g, lambda o: o.copy_(sums[C:2 * C]), ctx.needs_input_grad[1])
+        db = _emit(b, lambda o: o.copy_(sums[:C]), ctx.needs_input_grad[2])
+        da = _emit(a, lambda o: o.copy_(sums[2 * C:].view_as(o)), ctx.needs_input_grad[5])
+        return dx, dg, db, None, None, da, None, None, None
+
+
+def bn_prelu(x, gamma, beta, rmean, rvar, slope, training=True, momentum=0.1, eps=1e-5):
+    return BnPreluFn.apply(x, gamma, beta, rmean, rvar, slope, bool(training), float(momentum), float(eps))
+
+
+class UpsampleNhwcFn(torch.autograd.Function):
+    """Upsample(x, size) (bilinear, align_corners=False; model_stage2.py:29-35) of channels-last x [B,Hi,Wi,C], with the top-down
+    path's skip add (:127-129): -> up [B,Ho,Wo,C] and, when skip is given, up + skip as a second output."""
+
+    @staticmethod
+    def forward(ctx, x, skip, Ho, Wo):
+        _chk(x, skip)
+        x = unplanes(x).contiguous()
+        B, Hi, Wi, C = x.shape
+        if Ho < Hi or Wo < Wi:
+            raise ValueError(f"upsample_nhwc upsamples ({Hi}x{Wi} -> {Ho}x{Wo} would shrink): its backward is the gather form for Ho >= Hi, Wo >= Wi")
+        up = torch.empty(B, Ho, Wo, C, device=x.device, dtype=torch.float32)
+        s = None
+        if skip is not None:
+            skip = unplanes(skip).contiguous()
+            if tuple(skip.shape) != (B, Ho, Wo, C):
+                raise ValueError(f"skip {tuple(skip.shape)} does not match the upsampled map {(B, Ho, Wo, C)}")
+            s = torch.empty_like(up)
+        call("tris_upsample_nhwc_fwd_f32", P(x), P(skip), P(up), P(s), B, Hi, Wi, Ho, Wo, C, _stream())
+        ctx.cfg = (B, Hi, Wi, Ho, Wo, C, skip is not None)
+        return (up, s) if s is not None else up
+
+    @staticmethod
+    def backward(ctx, d_up, d_sum=None):
+        B, Hi, Wi, Ho, Wo, C, has_skip = ctx.cfg
+        d_up = None if d_up is None else unplanes(pl_grad_in(d_up.contiguous()))
+        d_sum = None if d_sum is None else unplanes(pl_grad_in(d_sum.contiguous()))
+        dx = None
+        if ctx.needs_input_grad[0] and (d_up is not None or d_sum is not None):
+            dx = torch.empty(B, Hi, Wi, C, device=(d_up if d_up is not None else d_sum).device, dtype=torch.float32)
+            call("tris_upsample_nhwc_bwd_f32", P(d_up), P(d_sum), P(dx), B, Hi, Wi, Ho, Wo, C, _stream())
+        return dx, (d_sum if has_skip else None), None, None
+
+
+def upsample_nhwc(x, size, skip=None):
+    """-> up, or (up, up + skip) with a skip"""
+    return UpsampleNhwcFn.apply(x, skip, int(size[0]), int(size[1]))
+
+
+class Head1Fn(torch.autograd.Function):
+    """nn.Conv2d(C, 1, 1, bias=False) on channels-last x [B,h,w,C] (final_seg1..4[1], model_stage2.py:75-86) -> [B,1,h,w]
+    (one channel: the NCHW and channels-last layouts coincide)"""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        _chk(x, w)
+        x = unplanes(x).contiguous()
+        B, h, wd, C = x.shape
+        if w.numel() != C:
+            raise ValueError(f"head weight {tuple(w.shape)} does not take {C} channels")
+        wf = w.detach().reshape(C).contiguous()
+        y = torch.empty(B, 1, h, wd, device=x.device, dtype=torch.float32)
+        call("tris_head1_fwd_f32", P(x), P(wf), P(y), B * h * wd, C, _stream())
+        ctx.params = (w,)
+        ctx.save_for_backward(x, wf)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, wf = ctx.saved_tensors
+        B, h, wd, C = x.shape
+        M = B * h * wd
+        g = g.contiguous()
+        dx = torch.empty_like(x)
+        dw = torch.empty(C, device=x.device, dtype=torch.float32)
+        ws = workspace(query("tris_seg_workspace_bytes", M, C))
+        call("tris_head1_bwd_f32", P(g), P(x), P(wf), P(dx), P(dw), M, C, P(ws), _stream())
+        dW = _emit(ctx.params[0], lambda o: o.copy_(dw.view_as(o)), ctx.needs_input_grad[1])
+        return (dx if ctx.needs_input_grad[0] else None), dW
+
+
+def head1x1(x, w):
+    return Head1Fn.apply(x, w)
+
+
+class Bce4Fn(torch.autograd.Function):
+    """criterion (model_stage2.py:139-141) of up to four heads against one target, summed as train_stage2.py:314-319 does:
+    -> losses[5] = (l1 + l2 + l3 + l4, l1, l2, l3, l4); x2..x4 may be None (loss 0).  The target is read as int64 (the pseudo masks)
+    or fp32; other dtypes are converted to fp32 first, as the reference's target.float()."""
+
+    @staticmethod
+    def forward(ctx, target, x1, x2, x3, x4):
+        xs = [None if x is None else x.contiguous() for x in (x1, x2, x3, x4)]
+        _chk(target, *xs)
+        if target.dtype not in (torch.int64, torch.float32):
+            target = target.float()
+        target = target.contiguous()
+        n = target.numel()
+        for x in xs:
+            if x is not None and x.numel() != n:
+                raise ValueError(f"head output {tuple(x.shape)} does not match the target {tuple(target.shape)}")
+        kind = int(target.dtype == torch.float32)
+        losses = torch.empty(5, device=target.device, dtype=torch.float32)
+        ws = workspace(query("tris_bce4_workspace_bytes", n))
+        call("tris_bce4_fwd_f32", *[P(x) for x in xs], P(target), kind, n, P(losses), P(ws), _stream())
+        ctx.kind = kind
+        ctx.save_for_backward(target, *xs)
+        return losses
+
+    @staticmethod
+    def backward(ctx, g):
+        target, *xs = ctx.saved_tensors
+        g = g.contiguous()
+        ds = [None if x is None or not ctx.needs_input_grad[1 + k] else torch.empty_like(x) for k, x in enumerate(xs)]
+        call("tris_bce4_bwd_f32", *[P(x) for x in xs], P(target), ctx.kind, P(g), *[P(d) for d in ds], target.numel(), _stream())
+        return (None, *ds)
+
+
+def bce4(outs, target):
+    return Bce4Fn.apply(target, *outs)
+
+
+def bce(out, target):
+    """one head: F.binary_cross_entropy_with_logits(out, target.float(), reduction='mean') as a 0-d tensor"""
+    return Bce4Fn.apply(target, out, None, None, None)[1]
+
+
+def eval_post_signed(seg_map, target_u8):
+    """validate.py:179-191 for one (image, sentence) of a SIGNED map (Stage-2 logits): normalised by max + 1e-5 whatever its sign.
+    -> (iu int64[3] on device = I, U, first arg-max of the normalised map; cam [oH,oW])"""
+    _chk(seg_map, target_u8)
+    S = seg_map.shape[-1]
+    if seg_map.shape[-2] != S:
+        raise ValueError(f"eval_post_signed takes a square map (validate feeds size x size inputs), got {tuple(seg_map.shape)}")
+    oH, oW = target_u8.shape[-2:]
+    cam = torch.empty(oH, oW, device=seg_map.device, dtype=torch.float32)
+    iu = torch.empty(3, device=seg_map.device, dtype=torch.int64)
+    ws = workspace(4 * (2049 + 4 * 1024 + 8))
+    call("tris_eval_post_signed_f32", P(seg_map.contiguous()), S, P(target_u8.contiguous()), oH, oW, P(cam), P(iu), P(ws),
+         _stream())
+    return iu, cam

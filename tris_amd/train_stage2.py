@@ -1,0 +1,168 @@
+"""TRIS Stage-2 training on MI355X -- drop-in for the reference's `train_stage2.py`: the pseudo-mask decoder trained with
+`criterion` on the four heads (train_stage2.py:314-319), AdamW over the two parameter groups of `trainable_parameters`
+(:133-138; as FusedAdamW), the poly-0.9 LambdaLR stepped once per EPOCH (:192 -- its lambda counts iterations, so the rate barely
+decays; Stage-1 steps it per iteration), validation after every epoch with the best and best-hit checkpoints, `--resume --eval`,
+and the final evaluation of the train split with the best checkpoint (:229-247).
+
+    python -m tris_amd.train_stage2 --pseudo_path <dir> <the reference's flags>
+
+Single GPU, eager steps (the reference's Stage-2 script is single-GPU: --distributed raises).  EMA consistency training
+(--model_ema) needs `ema_pytorch`, which is not on this stack: it raises.  The aux ViT-B/32 the reference loads (:170) is never
+used without EMA and is not loaded.
+"""
+import datetime
+import os
+import time
+
+import torch
+
+from . import ops
+from .train_stage1 import _logger, build_loader, setup_seed
+
+
+def _check_args(args):
+    if getattr(args, "model_ema", False):
+        raise NotImplementedError("--model_ema: EMA consistency training needs the ema_pytorch package (train_stage2.py:22), "
+                                  "which is not on this stack; Stage-2 trains without EMA (l5 = 0)")
+    if getattr(args, "distributed", False):
+        raise NotImplementedError("--distributed: the reference's Stage-2 script trains on a single GPU "
+                                  "(scripts/train_stage2.sh); data-parallel Stage-2 is not implemented")
+
+
+def train_step(model, optimizer, img, word_ids, pseudo):
+    """forward -> the four BCE losses -> backward -> AdamW, bracketed as one h2 step (train_stage1._step_body).
+    -> device tensor losses[5] = (loss, l1, l2, l3, l4), detached (no host sync)"""
+    ops.h2_begin_step()
+    outs = model(img, word_ids)
+    losses = ops.bce4(outs, pseudo)
+    optimizer.zero_grad()
+    losses[0].backward()
+    optimizer.step()
+    ops.h2_end_step()
+    return losses.detach()
+
+
+def train_one_epoch(train_loader, model, optimizer, epoch, local_rank, args, iteration=0, clip_model=None, model_ema=None):
+    """The reference's signature and batch-dict contract (train_stage2.py:260); returns `iteration`."""
+    _check_args(args)
+    if model_ema is not None:
+        raise NotImplementedError("model_ema: EMA consistency training is not implemented on this stack")
+    model.train()
+    num_steps = len(train_loader)
+    t0 = time.time()
+    for idx, (samples, targets) in enumerate(train_loader):
+        word_ids = samples["word_ids"].squeeze(1).cuda(local_rank, non_blocking=True)
+        img = samples["img"].cuda(local_rank, non_blocking=True)
+        pseudo = targets["pseudo_gt"].cuda(local_rank, non_blocking=True)
+        last = train_step(model, optimizer, img, word_ids, pseudo)
+        if idx % args.print_freq == 0 and local_rank == 0:
+            v = last.tolist()   # the only host sync, every print_freq steps
+            print(f"Train:[{epoch:2d}/{args.epoch}][{idx:4d}/{num_steps}] | lr {optimizer.param_groups[0]['lr']:.6f} || "
+                  f"loss: {v[0]:.4f} | l1: {v[1]:.4f} | l2: {v[2]:.4f} | l3: {v[3]:.4f} | l4: {v[4]:.4f} | l5: 0.0000 | "
+                  f"time/step: {(time.time() - t0) / (idx + 1):.4f}", flush=True)
+        iteration += 1
+    print(f"EPOCH {epoch} training takes {datetime.timedelta(seconds=int(time.time() - t0))}", flush=True)
+    return iteration
+
+
+def build_dataset(args, split, train, eval_mode, pseudo_path=None, tokenizer=None):
+    """ReferDataset with the reference's Stage-2 arguments (train_stage2.py:72-93)"""
+    from .dataset.ReferDataset import ReferDataset
+    from .dataset.transform import get_transform
+    return ReferDataset(refer_data_root=args.refer_data_root, dataset=args.dataset, splitBy=args.splitBy,
+                        bert_tokenizer=args.bert_tokenizer, split=split, size=args.size, max_tokens=args.max_query_len,
+                        image_transforms=get_transform(args.size, train=train), eval_mode=eval_mode, pseudo_path=pseudo_path,
+                        tokenizer=tokenizer)
+
+
+def main(args, tokenizer=None):
+    """tokenizer: as train_stage1.main (an extension; default the CLIP tokenizer)"""
+    _check_args(args)
+    from torch.utils.data import DataLoader
+    from .model.model_stage2 import TRIS
+    from .optim import FusedAdamW
+    from .utils.util import load_checkpoint, load_pretrained_checkpoint, save_checkpoint
+    from .validate import validate
+    local_rank = 0
+    log = _logger(args, local_rank)
+    model = TRIS(args).cuda()
+    param_groups = model.trainable_parameters()
+    model.train()
+    log.info(f"number of params: {sum(p.numel() for p in model.parameters() if p.requires_grad) / 1e6:.2f}M")
+
+    val_sets = [build_dataset(args, sp, train=False, eval_mode=True, tokenizer=tokenizer) for sp in args.test_split.split(",")]
+    val_loaders = [build_loader(args, v, 1, False, False) for v in val_sets]
+
+    def evaluate(loaders):
+        return [validate(args, vl, model, local_rank, logger=log) for vl in loaders]
+
+    optimizer = FusedAdamW([
+        {"params": param_groups[0], "lr": args.lr * args.lr_multi, "weight_decay": args.weight_decay},
+        {"params": param_groups[1], "lr": args.lr, "weight_decay": args.weight_decay},
+    ], lr=args.lr, weight_decay=args.weight_decay)
+
+    if args.resume and args.eval:
+        load_checkpoint(args, model, optimizer, None, log)
+        t0 = time.time()
+        res = evaluate(val_loaders)
+        acc = [float(r[1]) for r in res] + [0.0, 0.0]
+        print(f"val: {acc[0]}, testA, {acc[1]}, testB: {acc[2]}")
+        print(f"Testing time:  {datetime.timedelta(seconds=int(time.time() - t0))}")
+        return res
+
+    if args.pseudo_path is None:
+        raise ValueError("Stage-2 training needs --pseudo_path (the directory of the pseudo masks)")
+    train_set = build_dataset(args, "train", train=True, eval_mode=False, pseudo_path=args.pseudo_path,
+                              tokenizer=tokenizer)
+    # the reference's DataLoader path (pseudo masks are not part of the HBM cache)
+    train_loader = DataLoader(train_set, batch_size=args.batch_size, num_workers=2, pin_memory=True, shuffle=True)
+    steps_total = max(len(train_loader) * args.epoch, 1)
+    scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lambda x: (1 - x / steps_total) ** 0.9)
+    if args.resume:
+        load_checkpoint(args, model, optimizer, scheduler, log)
+    if args.pretrained_checkpoint is not None:
+        print("loading ", args.pretrained_checkpoint)
+        load_pretrained_checkpoint(args.pretrained_checkpoint, model)
+
+    log.info("Start training")
+    best = {"val_acc": -1, "val_hit": -1, "epoch": -1, "path": "", "hit": -1, "hit_path": "", "testA": -1, "testB": -1}
+    iteration, train_time, start = 0, 0.0, time.time()
+    for epoch in range(args.start_epoch, args.epoch):
+        t0 = time.time()
+        iteration = train_one_epoch(train_loader, model, optimizer, epoch, local_rank, args, iteration)
+        scheduler.step()                  # once per EPOCH, as train_stage2.py:192
+        torch.cuda.synchronize()
+        train_time += time.time() - t0
+        res = evaluate(val_loaders)
+        oIoU, val_acc, hit = res[0]
+        if float(val_acc) > best["val_acc"]:
+            if os.path.exists(best["path"]):
+                os.remove(best["path"])
+            best.update(path=save_checkpoint(epoch, model, optimizer, scheduler, log, args, f"ckpt_320_epoch_{epoch}.pth"),
+                        val_acc=float(val_acc), val_hit=hit, epoch=epoch,
+                        testA=float(res[1][1]) if len(res) > 1 else 0, testB=float(res[2][1]) if len(res) > 2 else 0)
+        if hit > best["hit"]:
+            if os.path.exists(best["hit_path"]):
+                os.remove(best["hit_path"])
+            best.update(hit_path=save_checkpoint(epoch, model, optimizer, scheduler, log, args, f"ckpt_320_epoch_{epoch}_hit.pth"),
+                        hit=hit)
+        print(best, flush=True)
+
+    # the train split, evaluated with the best checkpoint (train_stage2.py:229-247)
+    if best["path"]:
+        print("loading ", best["path"])
+        load_pretrained_checkpoint(best["path"], model)
+        train_eval = build_loader(args, build_dataset(args, "train", train=False, eval_mode=True, tokenizer=tokenizer), 1, False,
+                                   False)
+        oIoU, mIoU, hit = evaluate([train_eval])[0]
+        print("Validat on the train split: ", oIoU, mIoU, hit)
+    print(best)
+    log.info(f"Training time {train_time:.1f}s; training + testing {datetime.timedelta(seconds=int(time.time() - start))}")
+    return best
+
+
+if __name__ == "__main__":
+    from .args import get_parser
+    _a = get_parser().parse_args()
+    setup_seed(1234)
+    main(_a)

@@ -175,3 +175,23 @@ def word_hash_tokenize(texts, context_length=77, truncate=False):
         ids = ids[:context_length]
         out[i, :len(ids)] = torch.tensor(ids)
     return out
+
+
+def make_pseudo_masks(root, out_dir, seed=0, dataset="refcocog", splitBy="umd"):
+    """Synthetic Stage-2 pseudo masks for every train ref of a make_mini_refer dataset, in the layout the reference reads
+    (dataset/ReferDataset.py:178-186): out_dir/{index}_{img_id}.npy = pickled {'mask': bool [2, h, w]} -- two instances that
+    overlap, so the summed target holds 0, 1 and 2.  index = position of the ref in the train split."""
+    import os
+    from ..dataset.refer import REFER
+    refer = REFER(root, dataset, splitBy)
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.RandomState(seed)
+    for i, ref_id in enumerate(refer.getRefIds(split="train")):
+        img_id = refer.getImgIds(ref_id)[0]
+        h, w = refer.Imgs[img_id]["height"], refer.Imgs[img_id]["width"]
+        mk = np.zeros((2, h, w), dtype=bool)
+        y0, x0 = rng.randint(0, max(h // 2, 1)), rng.randint(0, max(w // 2, 1))
+        mk[0, y0:y0 + h // 2, x0:x0 + w // 2] = True
+        mk[1, h // 4:, w // 4:] = True
+        np.save(os.path.join(out_dir, f"{i}_{img_id}.npy"), {"mask": mk}, allow_pickle=True)
+    return out_dir

@@ -78,6 +78,10 @@ def validate(args, data_loader, model, local_rank=0, visualize=False, logger=Non
     cam_out_name = []
     graphs = {}
     group = max(1, int(cfg.eval_group))
+    # Stage-2 models (model_stage2.TRIS.signed_maps) produce signed logit maps: validate.py:179-191 normalises them by their max
+    # whatever its sign, which ops.eval_post_signed restates; the Stage-1 relu maps keep ops.eval_post
+    signed = bool(getattr(net, "signed_maps", False))
+    post = ops.eval_post_signed if signed else ops.eval_post
     end = time.time()
 
     def account(idx, j, img_id, bbox, I, U, am, cam, n_img):
@@ -114,7 +118,7 @@ def validate(args, data_loader, model, local_rank=0, visualize=False, logger=Non
         ius, cams, k = [], [], 0
         for r in refs:
             for _ in range(r[3].size(-1)):
-                iu, cam = ops.eval_post(maps[k:k + 1], r[4])
+                iu, cam = post(maps[k:k + 1], r[4])
                 ius.append(iu)
                 cams.append(cam)
                 k += 1
@@ -148,15 +152,18 @@ def validate(args, data_loader, model, local_rank=0, visualize=False, logger=Non
                     flush(pending)
                     pending = []
                 continue
-            gr = _graphed(net, img, word_ids.shape[1], graphs)
+            gr = None if signed else _graphed(net, img, word_ids.shape[1], graphs)
             if gr is not None:
                 gr.visual(img)                                                                 # once per image (hipGraph)
             else:
                 vis = net.encode_visual(img)
             for j in range(word_ids.size(-1)):
                 wid = word_ids[:, :, j].contiguous()
-                out = gr.sentence(wid) if gr is not None else net.forward_cached(vis, wid, img.shape[2])  # [1,1,H,W]
-                iu, cam = ops.eval_post(out, tgt)
+                if signed:
+                    out = net.forward_pairs(vis, wid, [0], img.shape[2])                       # [1,1,H,W]
+                else:
+                    out = gr.sentence(wid) if gr is not None else net.forward_cached(vis, wid, img.shape[2])  # [1,1,H,W]
+                iu, cam = post(out, tgt)
                 I, U, am = iu.tolist()                                                         # the one host sync
                 account(idx, j, img_id, bbox, I, U, am, cam, img.size(0))
             batch_time.update(time.time() - end)
