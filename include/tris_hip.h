@@ -612,6 +612,55 @@ int tris_bce4_bwd_f32(const float* x1, const float* x2, const float* x3, const f
 int tris_eval_post_signed_f32(const float* map, int S, const unsigned char* target, int oH, int oW, float* cam, long* out_iu,
                               float* workspace, void* stream);
 
+/* ---- Instance-mask synthesis (csrc/insseg.hip; irn.py): the post-network half of IRNet's make_ins_seg_labels --------------
+ * (response map, edge map [h,w], displacement field [2,h,w]) -> instance masks, the pseudo labels Stage 2 trains on.  Reference
+ * lines are those of IRNet/step_refer/make_ins_seg_labels.py ("labels.py") and IRNet/misc/indexing.py.  f32 on the vector ALU;
+ * the dense N x N transition matrix of indexing.py:112-139 is never formed. */
+/* find_centroids_with_refinement (labels.py:18-56): `iterations` steps of bilinear gather at (ceil, floor), move, clip; then
+ * round half to even.  centroids int32 [2,h,w] = (y, x).  The reference's numpy expression promotes to float64 (float32 minus
+ * int32) and rounds to float32 once per step; the kernel does the same operations in the same order without contraction, so the
+ * result is bit-identical. */
+int tris_irn_centroids_f32(const float* dp, int h, int w, int iterations, int* centroids, void* stream);
+/* cluster_centroids (labels.py:61-64): mask = sqrt(dp[1]^2 + dp[0]^2) < thres, uint8 [h,w] */
+int tris_irn_weak_mask_f32(const float* dp, int h, int w, float thres, unsigned char* mask, void* stream);
+/* skimage.measure.label(img, connectivity=1, background=0) (labels.py:66, :92) of B images uint8 [B,H,W]: labels int32 [B,H,W]
+ * numbered 1..counts[b] by each component's first pixel in raster order, 0 on the background.  Union-find whose root is the
+ * component's minimum linear index (pixels start linked to the neighbour above or to the left), then a rank pass over the roots: deterministic and order-exact.  B <= 65535.
+ * workspace: tris_cc_workspace_bytes(B, H, W). */
+long tris_cc_workspace_bytes(int B, int H, int W);
+int tris_cc_label_u8(const unsigned char* img, int B, int H, int W, int* labels, int* counts, int* workspace, void* stream);
+/* cluster_centroids (labels.py:67-75): inst_map[p] = rank, among the values that occur, of dp_label[centroid of p]
+ * (imutils.compress_range of the label + 1); n_inst[0] = the number of instances K.  dp_label holds 0..n_label.
+ * workspace: n_label + 1 ints. */
+int tris_irn_cluster_i32(const int* centroids, const int* dp_label, int n_label, int h, int w, int* inst_map, int* n_inst,
+                         int* workspace, void* stream);
+/* separte_score_by_mask (labels.py:77-80): out[k][p] = inst_map[p] == k ? cam[p] : 0, out [K,n] */
+int tris_irn_instance_cam_f32(const float* cam, const int* inst_map, int K, int n, float* out, void* stream);
+/* PathIndex + edge_to_affinity + torch.pow + the column sum (indexing.py:18-109, :132-135, :141-158): Wt[d][p] =
+ * (1 - max of edge over the path cells from p to p + dirs[d]) ^ beta, 0 where p + dirs[d] is outside the map (the reference's
+ * padding with 1.0); colsum[p] = 1 + the weights of the 2 n_dirs pairs incident to p.  dirs int32 [n_dirs,2] = (dy, dx) with
+ * dy >= 0; path cells of direction d: path_cells[path_off[d] .. path_off[d+1]) as (dy, dx), both ends included (host tables,
+ * irn.search_paths).  Wt [n_dirs, h*w], colsum [h*w]. */
+int tris_irn_affinity_f32(const float* edge, int h, int w, const int* dirs, const int* path_off, const int* path_cells, int n_dirs,
+                          float beta, float* Wt, float* colsum, void* stream);
+/* propagate_to_edge (indexing.py:160-164): v0 = x (1 - edge), then `steps` = 2^exp_times products v <- v T as gathers
+ * v[j] <- (v[j] + sum_d Wt[d][j] v[j+dir_d] + Wt[d][j-dir_d] v[j-dir_d]) / colsum[j] for K rows; x, out [K, h*w].
+ * One launch per step; the rows ping-pong between out and tmp [K, h*w], any map size. */
+int tris_irn_walk_f32(const float* x, const float* edge, const float* Wt, const float* colsum, const int* dirs, int n_dirs, int K,
+                      int h, int w, int steps, float* out, float* tmp, void* stream);
+/* labels.py:146-157: rw_up = F.interpolate(rw, scale_factor=4, bilinear, align_corners=False) cropped to (H, W), divided by its
+ * global maximum; labels = argmax over [bg_thres, rw_up[0], ...] (first maximum wins: the background wins ties).  rw [K,h,w],
+ * rw_up [K,H,W], labels int32 [H,W] in 0..K.  H <= 4h, W <= 4w.  workspace >= 1025 floats. */
+int tris_irn_finish_f32(const float* rw, int K, int h, int w, int H, int W, float bg_thres, float* rw_up, int* labels,
+                        float* workspace, void* stream);
+/* pyutils.to_one_hot (labels.py:75, :157): masks[k][i] = labels[i] == k + base, uint8 [K,n]; base = 1 is to_one_hot(labels)[1:] */
+int tris_irn_label_masks_u8(const int* labels, int K, long n, int base, unsigned char* masks, void* stream);
+/* detect_instance (labels.py:82-105) after tris_cc_label_u8 of the K masks: fragment g = offsets[k] + f - 1 for label f of row k
+ * (offsets = exclusive prefix of the counts, F their sum): frag_masks uint8 [F,n], area int32 [F], score [F] =
+ * max(rw_up[k] * mask) or 0 where area < min_area.  workspace: F ints. */
+int tris_irn_fragments_f32(const int* frag_labels, const float* rw_up, const int* offsets, int K, long n, long min_area, int F,
+                           float* score, int* area, unsigned char* frag_masks, int* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

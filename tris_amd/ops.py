@@ -3114,3 +3114,137 @@ def eval_post_signed(seg_map, target_u8):
     call("tris_eval_post_signed_f32", P(seg_map.contiguous()), S, P(target_u8.contiguous()), oH, oW, P(cam), P(iu), P(ws),
          _stream())
     return iu, cam
+
+
+# ------------------------------------------------------------------------------------- instance-mask synthesis (IRNet tail)
+# csrc/insseg.hip; the public functions with the reference's names are in tris_amd/irn.py
+def _chk_t(t, dtype):
+    if not t.is_cuda:
+        raise NoGpuError("tris_amd ops run on MI355X only (got a CPU tensor); there is no CPU fallback")
+    if t.dtype != dtype:
+        raise TypeError(f"expected {dtype}, got {t.dtype}")
+    return t.contiguous()
+
+
+def irn_centroids(dp, iterations=300):
+    """find_centroids_with_refinement: dp float32 [2,h,w] -> int32 [2,h,w] (y, x), bit-identical to the reference's numpy"""
+    dp = _chk_t(dp, torch.float32)
+    _, h, w = dp.shape
+    out = torch.empty(2, h, w, dtype=torch.int32, device=dp.device)
+    call("tris_irn_centroids_f32", P(dp), h, w, int(iterations), P(out), _stream())
+    return out
+
+
+def irn_weak_mask(dp, thres=2.5):
+    """sqrt(dp[1]^2 + dp[0]^2) < thres as uint8 [h,w]"""
+    dp = _chk_t(dp, torch.float32)
+    _, h, w = dp.shape
+    out = torch.empty(h, w, dtype=torch.uint8, device=dp.device)
+    call("tris_irn_weak_mask_f32", P(dp), h, w, float(thres), P(out), _stream())
+    return out
+
+
+def cc_label(img):
+    """skimage.measure.label(connectivity=1, background=0) of uint8 [H,W] or [B,H,W] -> (labels int32 of the same shape, counts
+    int32 [B] on device)"""
+    img = _chk_t(img, torch.uint8)
+    H, W = img.shape[-2:]
+    B = img.numel() // max(H * W, 1) if img.dim() == 3 else 1
+    labels = torch.empty(img.shape, dtype=torch.int32, device=img.device)
+    counts = torch.zeros(B, dtype=torch.int32, device=img.device)
+    if B * H * W:
+        ws = workspace(query("tris_cc_workspace_bytes", B, H, W))
+        call("tris_cc_label_u8", P(img), B, H, W, P(labels), P(counts), P(ws), _stream())
+    return labels, counts
+
+
+def irn_cluster(centroids, dp_label, n_label):
+    """cluster_centroids' gather + compress_range: -> (instance map int32 [h,w] in 0..K-1, K int32 [1] on device)"""
+    centroids = _chk_t(centroids, torch.int32)
+    dp_label = _chk_t(dp_label, torch.int32)
+    _, h, w = centroids.shape
+    inst = torch.empty(h, w, dtype=torch.int32, device=centroids.device)
+    k = torch.empty(1, dtype=torch.int32, device=centroids.device)
+    ws = workspace(4 * (int(n_label) + 1))
+    call("tris_irn_cluster_i32", P(centroids), P(dp_label), int(n_label), h, w, P(inst), P(k), P(ws), _stream())
+    return inst, k
+
+
+def irn_instance_cam(cam, inst_map, K):
+    """separte_score_by_mask: cam [h,w], instance map int32 [h,w] -> [K,h,w]"""
+    cam = _chk_t(cam, torch.float32)
+    inst_map = _chk_t(inst_map, torch.int32)
+    h, w = cam.shape
+    out = torch.empty(K, h, w, dtype=torch.float32, device=cam.device)
+    call("tris_irn_instance_cam_f32", P(cam), P(inst_map), K, h * w, P(out), _stream())
+    return out
+
+
+def irn_affinity(edge, dirs, path_off, path_cells, beta=10):
+    """edge [h,w] -> (Wt [n_dirs, h, w] = a^beta towards each search direction, colsum [h,w]); tables: irn.device_tables"""
+    edge = _chk_t(edge, torch.float32)
+    dirs, path_off, path_cells = (_chk_t(t, torch.int32) for t in (dirs, path_off, path_cells))
+    h, w = edge.shape
+    nd = dirs.shape[0]
+    Wt = torch.empty(nd, h, w, dtype=torch.float32, device=edge.device)
+    colsum = torch.empty(h, w, dtype=torch.float32, device=edge.device)
+    call("tris_irn_affinity_f32", P(edge), h, w, P(dirs), P(path_off), P(path_cells), nd, float(beta), P(Wt), P(colsum), _stream())
+    return Wt, colsum
+
+
+def irn_walk(x, edge, Wt, colsum, dirs, steps):
+    """`steps` products v <- v T from v0 = x (1 - edge): x [K,h,w] -> [K,h,w]; one launch per step, any map size"""
+    x, edge, Wt, colsum = (_chk_t(t, torch.float32) for t in (x, edge, Wt, colsum))
+    dirs = _chk_t(dirs, torch.int32)
+    K, h, w = x.shape
+    out = torch.empty(K, h, w, dtype=torch.float32, device=x.device)
+    tmp = torch.empty_like(out)
+    call("tris_irn_walk_f32", P(x), P(edge), P(Wt), P(colsum), P(dirs), dirs.shape[0], K, h, w, int(steps), P(out), P(tmp),
+         _stream())
+    return out
+
+
+def irn_finish(rw, size, bg_thres=0.25):
+    """x4 bilinear upsample (align_corners=False) cropped to size, / global max, arg-max against the background:
+    rw [K,h,w] -> (rw_up [K,H,W], labels int32 [H,W] in 0..K)"""
+    rw = _chk_t(rw, torch.float32)
+    K, h, w = rw.shape
+    H, W = int(size[0]), int(size[1])
+    if K < 1 or not (0 < H <= 4 * h and 0 < W <= 4 * w):
+        raise ValueError(f"irn_finish: K={K}, map {h}x{w}, size {H}x{W}")
+    up = torch.empty(K, H, W, dtype=torch.float32, device=rw.device)
+    labels = torch.empty(H, W, dtype=torch.int32, device=rw.device)
+    ws = workspace(4 * 1032)
+    call("tris_irn_finish_f32", P(rw), K, h, w, H, W, float(bg_thres), P(up), P(labels), P(ws), _stream())
+    return up, labels
+
+
+def irn_label_masks(labels, K, base=1):
+    """to_one_hot: int32 [H,W] -> uint8 [K,H,W], plane k = (labels == k + base); base 1 is to_one_hot(labels)[1:]"""
+    labels = _chk_t(labels, torch.int32)
+    H, W = labels.shape
+    masks = torch.empty(K, H, W, dtype=torch.uint8, device=labels.device)
+    call("tris_irn_label_masks_u8", P(labels), K, H * W, int(base), P(masks), _stream())
+    return masks
+
+
+def irn_fragments(frag_labels, counts, rw_up, min_area):
+    """detect_instance's fragments from the labelled masks: frag_labels int32 [K,H,W], counts: K Python ints ->
+    (score float32 [F], area int32 [F], masks uint8 [F,H,W]), fragments in (row, label) order"""
+    frag_labels = _chk_t(frag_labels, torch.int32)
+    rw_up = _chk_t(rw_up, torch.float32)
+    K, H, W = frag_labels.shape
+    offs, F = [], 0
+    for c in counts:
+        offs.append(F)
+        F += int(c)
+    dev = rw_up.device
+    score = torch.empty(F, dtype=torch.float32, device=dev)
+    area = torch.empty(F, dtype=torch.int32, device=dev)
+    masks = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
+    if F:
+        offsets = torch.tensor(offs, dtype=torch.int32).to(dev)
+        ws = workspace(4 * F)
+        call("tris_irn_fragments_f32", P(frag_labels), P(rw_up), P(offsets), K, H * W, int(min_area), F, P(score), P(area),
+             P(masks), P(ws), _stream())
+    return score, area, masks

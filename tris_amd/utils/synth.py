@@ -195,3 +195,29 @@ def make_pseudo_masks(root, out_dir, seed=0, dataset="refcocog", splitBy="umd"):
         mk[1, h // 4:, w // 4:] = True
         np.save(os.path.join(out_dir, f"{i}_{img_id}.npy"), {"mask": mk}, allow_pickle=True)
     return out_dir
+
+
+def make_ins_seg_scene(H, W, n_blobs=2, seed=0):
+    """Synthetic inputs of tris_amd.irn.make_ins_seg for an H x W image: (cam float32 [H,W], edge float32 [h,w], dp float32
+    [2,h,w]) with h = (H-1)//4 + 1.  Round blobs whose displacement field points to their centre with strength 0.8 * distance
+    (above the 2.5 clustering threshold off the centre, so every blob is an instance of its own), an edge ring on every rim and
+    a response map that is high inside the blobs."""
+    rng = np.random.RandomState(seed)
+    h, w = (H - 1) // 4 + 1, (W - 1) // 4 + 1
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
+    dp = np.zeros((2, h, w), np.float32)
+    edge = (0.05 + 0.1 * rng.rand(h, w)).astype(np.float32)
+    low = (0.02 + 0.03 * rng.rand(h, w)).astype(np.float32)
+    rmax = max(5.0, min(h, w) / 4.0)
+    for b in range(n_blobs):
+        r = rng.uniform(5.0, rmax)
+        cy, cx = rng.uniform(r, max(h - 1 - r, r)), rng.uniform(r, max(w - 1 - r, r))
+        dist = np.sqrt((yy - cy) ** 2 + (xx - cx) ** 2)
+        inside = dist <= r
+        dp[0][inside] = ((cy - yy) * 0.8)[inside]
+        dp[1][inside] = ((cx - xx) * 0.8)[inside]
+        edge[np.abs(dist - r) < 0.8] = 0.92
+        low[dist < r - 1] = rng.uniform(0.5, 1.0)
+    # response map at the image's size: nearest-neighbour x4 of the low-resolution map, cropped
+    cam = np.repeat(np.repeat(low, 4, 0), 4, 1)[:H, :W].copy()
+    return cam, edge, dp
