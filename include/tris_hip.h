@@ -83,6 +83,8 @@ int tris_set_conv_direct_thread(int value);
  * once per product shape on first use and the fastest is cached for the process; 0 = the static cycle model (deterministic
  * run-to-run rounding). */
 int tris_set_autotune(int on);
+/* the current switch (1 | 0), for callers that turn it off around a region and restore it */
+int tris_get_autotune(void);
 int tris_get_gemm_mode(void);
 /* Diagnostics: launches so far of the direct 3x3 convolution kernels (kind 0: forward / data gradient) and of the direct 3x3
  * weight-gradient kernel (kind 1) -- the tests use it to prove which kernel ran.  Host-side counters, not thread-safe. */
@@ -660,6 +662,39 @@ int tris_irn_label_masks_u8(const int* labels, int K, long n, int base, unsigned
  * max(rw_up[k] * mask) or 0 where area < min_area.  workspace: F ints. */
 int tris_irn_fragments_f32(const int* frag_labels, const float* rw_up, const int* offsets, int K, long n, long min_area, int F,
                            float* score, int* area, unsigned char* frag_masks, int* workspace, void* stream);
+
+/* ---- IRNet edge / displacement network, inference (csrc/irnnet.hip; irn_net.py) --------------------------------------------
+ * What IRNet/net/resnet50_irn.py ("irn.py") and IRNet/net/resnet50.py ("resnet50.py") need beyond the dense products
+ * (tris_gemm_f32, tris_conv3x3_fwd_f32) and the frozen BatchNorm (tris_bn_apply_f32).  Channels-last, fp32, no atomics: every
+ * launch is bitwise reproducible. */
+/* stage1 up to the ReLU (resnet50.py:61-64, :95-97) on the loader's batch [img, flip_w(img)] (IRNet/voc12/dataloader.py:338-340):
+ * img uint8 [H][W][3]; lut [3][256] = the TorchvisionNormalize table (dataloader.py:77-79, float64 rounded once);
+ * Wk = conv1.weight as [7][7][3][64]; Y [2][Ho][Wo][64] = relu(bn1(conv1(x))) with tris_bn_apply_f32's expression,
+ * Ho = (H-1)/2 + 1.  Direct fp32 FMA kernel on the vector ALU. */
+int tris_irn_stem_f32(const unsigned char* img, const float* lut, const float* Wk, const float* mean, const float* invstd,
+                      const float* gamma, const float* beta, float* Y, int H, int W, void* stream);
+/* nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (resnet50.py:65): the padding never wins.  Y [B][(H-1)/2+1][(W-1)/2+1][C], C % 4 == 0 */
+int tris_maxpool3s2_f32(const float* X, float* Y, int B, int H, int W, int C, void* stream);
+/* the input gather of the strided 1x1 downsample convolution (resnet50.py:82-83): Y[b][i][j] = X[b][2i][2j] */
+int tris_subsample2_f32(const float* X, float* Y, int B, int H, int W, int C, void* stream);
+/* nn.GroupNorm(G, C) statistics (irn.py:31 ... :95) per image over HW pixels x C/G channels: fixed-order fp64 partials per row
+ * block, then one finalize; stats [B][G][2] = {mean, 1/sqrt(biased var + eps)}.  C <= 1024, 256 % (C/4) == 0, (C/G) % 4 == 0.
+ * workspace: tris_gn_workspace_bytes(B, HW, G). */
+long tris_gn_workspace_bytes(int B, long HW, int G);
+int tris_gn_stats_f32(const float* X, int B, long HW, int C, int G, float eps, float* stats, double* workspace, void* stream);
+/* GroupNorm apply -> nn.Upsample(scale_factor=scale, bilinear, align_corners=False) -> crop to (Ho, Wo) -> ReLU (irn.py:39-44,
+ * :125-127, :133-136), written with pixel pitch ldy floats (a channel slice of the torch.cat buffer of irn.py:128, :136-137):
+ * Y[b][oy][ox][c] for oy < Ho <= Hi*scale.  The blend is tris_upsample_nhwc_fwd_f32's.  scale = 1: no resampling.
+ * stats == NULL: no normalisation (upsample + crop only). */
+int tris_gn_apply_up_f32(const float* X, const float* stats, const float* gamma, const float* beta, float* Y, int B, int Hi, int Wi,
+                         int C, int G, int scale, int Ho, int Wo, long ldy, int relu, void* stream);
+/* the narrow heads fc_edge6 = nn.Conv2d(160, 1, 1, bias=True) (irn.py:57) and fc_dp7's nn.Conv2d(256, 2, 1) + MeanShift
+ * (irn.py:97-98, :114: bias = -running_mean): Y[m][n] = sum_c X[m*ldx + c] w[n][c] + bias[n] (bias may be NULL).
+ * N = 1 | 2, C % 32 == 0. */
+int tris_irn_head_f32(const float* X, long ldx, const float* w, const float* bias, float* Y, long M, int C, int N, void* stream);
+/* EdgeDisplacement.forward (irn.py:240-241): edge[y][x] = sigmoid(E[0][y][x]/2 + E[1][y][w-1-x]/2), dp[c][y][x] = D[0][y][x][c];
+ * E [2][h][w], D [2][h][w][2] */
+int tris_irn_net_finish_f32(const float* E, const float* D, float* edge, float* dp, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }

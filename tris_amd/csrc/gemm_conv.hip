@@ -994,6 +994,7 @@ extern "C" int tris_set_autotune(int on) {
   g_autotune = on ? 1 : 0;
   return 0;
 }
+extern "C" int tris_get_autotune(void) { return autotune_enabled() ? 1 : 0; }
 
 extern "C" int tris_get_gemm_mode(void) { return g_gemm_mode; }
 

@@ -6,8 +6,8 @@ can switch by importing this module:
     from tris_amd import irn
     rw = irn.propagate_to_edge(instance_cam, edge, beta=10, exp_times=8, radius=5)
 
-(response map, edge map, displacement field) come in as arrays; the edge / displacement network and its training are not on this
-stack ("Stage 2").  numpy inputs are moved to the GPU and numpy comes back; CUDA tensors stay tensors, except
+(response map, edge map, displacement field) come in as arrays; the edge / displacement network that produces the last two is
+tris_amd.irn_net (inference; its training is not on this stack: INTEGRATION.md, "Stage 2").  numpy inputs are moved to the GPU and numpy comes back; CUDA tensors stay tensors, except
 that detect_instance and make_ins_seg always return the reference's dict of numpy arrays.  There is
 no CPU path: without a GPU every function raises ops.NoGpuError.
 

@@ -3248,3 +3248,111 @@ def irn_fragments(frag_labels, counts, rw_up, min_area):
         call("tris_irn_fragments_f32", P(frag_labels), P(rw_up), P(offsets), K, H * W, int(min_area), F, P(score), P(area),
              P(masks), P(ws), _stream())
     return score, area, masks
+
+
+# --------------------------------------------------------------------------------- IRNet edge / displacement network (inference)
+# csrc/irnnet.hip; the module that strings them together is tris_amd/irn_net.py.  Inference only: no autograd Functions.
+class autotune_off:
+    """inside: dense products take the cost model's (tile, split-K) choice -- no first-encounter timing runs and no entry in the
+    per-process cache of tuned shapes (a network whose input size changes from call to call would add ~60 shapes per size)"""
+
+    def __enter__(self):
+        self.prev = int(_lib.load().tris_get_autotune())
+        set_autotune(False)
+        return self
+
+    def __exit__(self, *exc):
+        set_autotune(bool(self.prev))
+        return False
+
+
+def irn_stem(img_u8, lut, wk, mean, invstd, gamma, beta):
+    """img uint8 [H,W,3], lut [3,256], wk [7,7,3,64] -> relu(bn(conv7x7 s2 p3)) of [img, flip_w(img)]: [2,Ho,Wo,64]"""
+    img_u8 = _chk_t(img_u8, torch.uint8)
+    _chk(lut, wk, mean, invstd, gamma, beta)
+    H, W, C = img_u8.shape
+    if C != 3 or tuple(wk.shape) != (7, 7, 3, 64) or not wk.is_contiguous():
+        raise ValueError(f"irn_stem: image {tuple(img_u8.shape)}, weight {tuple(wk.shape)}")
+    y = torch.empty(2, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64, dtype=torch.float32, device=img_u8.device)
+    call("tris_irn_stem_f32", P(img_u8), P(lut.contiguous()), P(wk), P(mean), P(invstd), P(gamma), P(beta), P(y), H, W, _stream())
+    return y
+
+
+def maxpool3s2(x):
+    """nn.MaxPool2d(3, 2, 1) on channels-last [B,H,W,C]"""
+    x = _chk_t(x, torch.float32)
+    B, H, W, C = x.shape
+    y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, dtype=torch.float32, device=x.device)
+    call("tris_maxpool3s2_f32", P(x), P(y), B, H, W, C, _stream())
+    return y
+
+
+def subsample2(x):
+    """x[:, ::2, ::2, :] as a contiguous tensor (the gather of a stride-2 1x1 convolution)"""
+    x = _chk_t(x, torch.float32)
+    B, H, W, C = x.shape
+    y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, dtype=torch.float32, device=x.device)
+    call("tris_subsample2_f32", P(x), P(y), B, H, W, C, _stream())
+    return y
+
+
+def group_norm_stats(x, G, eps=1e-5):
+    """x [B,H,W,C] -> stats float32 [B,G,2] = (mean, 1/sqrt(var + eps)) per image and group; fixed-order fp64 sums"""
+    x = _chk_t(x, torch.float32)
+    B, H, W, C = x.shape
+    stats = torch.empty(B, G, 2, dtype=torch.float32, device=x.device)
+    ws = workspace(query("tris_gn_workspace_bytes", B, H * W, G))
+    call("tris_gn_stats_f32", P(x), B, H * W, C, G, float(eps), P(stats), P(ws), _stream())
+    return stats
+
+
+def gn_apply_up(x, stats, gamma, beta, G, scale=1, size=None, relu=False, out=None, c_off=0):
+    """relu?(crop(upsample_bilinear(groupnorm(x), x scale), size)) for x [B,Hi,Wi,C].  out [B,Ho,Wo,Ct] with c_off: the result
+    is written into channels [c_off, c_off + C) of `out` (a concatenation buffer).  stats None: no normalisation."""
+    x = _chk_t(x, torch.float32)
+    _chk(stats, gamma, beta)
+    B, Hi, Wi, C = x.shape
+    Ho, Wo = (Hi * scale, Wi * scale) if size is None else (int(size[0]), int(size[1]))
+    if out is None:
+        out = torch.empty(B, Ho, Wo, C, dtype=torch.float32, device=x.device)
+    if tuple(out.shape[:3]) != (B, Ho, Wo) or not out.is_contiguous() or c_off % 4 or c_off + C > out.shape[3]:
+        raise ValueError(f"gn_apply_up: out {tuple(out.shape)} does not take [{B},{Ho},{Wo},{C}] at channel {c_off}")
+    call("tris_gn_apply_up_f32", P(x), P(stats), P(gamma), P(beta), P(out, c_off), B, Hi, Wi, C, int(G), int(scale), Ho, Wo,
+         out.shape[3], int(relu), _stream())
+    return out
+
+
+def irn_head(x, w, bias=None):
+    """x [B,h,w,C] (C % 32 == 0), w [N,C] with N = 1 | 2 -> [B,h,w,N] = x . w^T + bias"""
+    x = _chk_t(x, torch.float32)
+    _chk(w, bias)
+    C = x.shape[-1]
+    N = w.numel() // C
+    M = x.numel() // C
+    y = torch.empty(*x.shape[:-1], N, dtype=torch.float32, device=x.device)
+    call("tris_irn_head_f32", P(x), C, P(w.contiguous()), P(bias), P(y), M, C, N, _stream())
+    return y
+
+
+def irn_net_finish(edge_out, dp_out):
+    """edge_out [2,h,w] (or [2,h,w,1]), dp_out [2,h,w,2] -> (edge [h,w] = sigmoid(row 0 / 2 + flip_w(row 1) / 2), dp [2,h,w] of row 0)"""
+    edge_out = _chk_t(edge_out, torch.float32)
+    dp_out = _chk_t(dp_out, torch.float32)
+    h, w = dp_out.shape[1:3]
+    edge = torch.empty(h, w, dtype=torch.float32, device=dp_out.device)
+    dp = torch.empty(2, h, w, dtype=torch.float32, device=dp_out.device)
+    call("tris_irn_net_finish_f32", P(edge_out), P(dp_out), P(edge), P(dp), h, w, _stream())
+    return edge, dp
+
+
+def bn_frozen(x, mean, invstd, gamma, beta, resid=None, relu=False):
+    """FixedBatchNorm (IRNet/net/resnet50.py:10-13): tris_bn_apply_f32 with running statistics and an invstd formed once at load
+    time; optional residual add and ReLU.  The pass leaves the amax of what it writes for the h2 product that reads it."""
+    _chk(x, mean, invstd, gamma, beta, resid)
+    x = x.contiguous()
+    C = x.shape[-1]
+    y = torch.empty_like(x)
+    h2_mark_next(y)
+    call("tris_bn_apply_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(None if resid is None else resid.contiguous()), P(y),
+         x.numel() // C, C, int(relu), _stream())
+    return y

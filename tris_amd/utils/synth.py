@@ -10,6 +10,8 @@ the benchmark and the CPU baseline share:
 * `synthetic_batch(B, size, L, negatives, seed)` -- images ~ N(0,1), token ids shaped like
   CLIP tokeniser output: SOT 49406, 2..17 random ids in [1, 49405], EOT 49407, zero padding.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -221,3 +223,46 @@ def make_ins_seg_scene(H, W, n_blobs=2, seed=0):
     # response map at the image's size: nearest-neighbour x4 of the low-resolution map, cropped
     cam = np.repeat(np.repeat(low, 4, 0), 4, 1)[:H, :W].copy()
     return cam, edge, dp
+
+
+def irn_fill(sd, seed=0, gain=1.0):
+    """Deterministic fill of an IRNet EdgeDisplacement state dict (tris_amd.irn_net; a ResNet-50 cannot be committed): sorted keys,
+    ONE generator.  Only the canonical names are filled (tris_amd.irn_net.canonical_name(k) == k); in the reference's own state
+    dict the aliases share their tensors with those, so both kinds of dict end up with the same values.  Rules:
+    num_batches_tracked -> 0;  running_mean 0.1 randn (the mean shift's included: non-zero);  running_var 1 + 0.1 rand;
+    norm scales (1-D .weight) 1 + 0.1 randn, halved for bn3 so that the residual sum grows by a few per cent per block, not by
+    sqrt(2);  1-D .bias 0.1 randn;  convolution weights gain * sqrt(2 / fan_in) randn, so that magnitudes survive 50 layers."""
+    from ..irn_net import canonical_name
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    for k in sorted(k for k in sd.keys() if canonical_name(k) == k):
+        t = sd[k]
+        shape = tuple(t.shape)
+        if k.endswith("num_batches_tracked"):
+            v = torch.zeros(shape)
+        elif k.endswith("running_mean"):
+            v = 0.1 * torch.randn(shape, generator=g)
+        elif k.endswith("running_var"):
+            v = 1.0 + 0.1 * torch.rand(shape, generator=g)
+        elif t.dim() == 1 and k.endswith(".weight"):
+            v = (0.5 if ".bn3." in k else 1.0) * (1.0 + 0.1 * torch.randn(shape, generator=g))
+        elif t.dim() == 1:
+            v = 0.1 * torch.randn(shape, generator=g)
+        else:
+            fan_in = t.shape[1] * t.shape[2] * t.shape[3]
+            v = gain * math.sqrt(2.0 / fan_in) * torch.randn(shape, generator=g)
+        with torch.no_grad():
+            t.copy_(v.to(t.dtype))
+    return sd
+
+
+def irn_image(H, W, seed=0, grey=False):
+    """a smooth uint8 test image [H,W,3] ([H,W] when grey) with some pixel noise: deterministic, no file needed"""
+    rng = np.random.RandomState(seed)
+    c = 1 if grey else 3
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    img = np.zeros((H, W, c))
+    for k in range(c):
+        fy, fx, ph = rng.uniform(0.02, 0.2, 2).tolist() + [rng.uniform(0, 6.28)]
+        img[..., k] = 127 + 90 * np.sin(fy * yy + ph) * np.cos(fx * xx - ph) + rng.uniform(-30, 30, (H, W))
+    img = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+    return img[..., 0] if grey else img
