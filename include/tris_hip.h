@@ -509,6 +509,11 @@ int tris_resample_u8(const unsigned char* in, int Hin, int Win, int C, const int
 /* Pillow NEAREST resize (dataset/transform.py:32, ReferDataset.py:187): out[y][x] = in[yidx[y]][xidx[x]] (index < 0 -> 0) */
 int tris_gather2d_u8(const unsigned char* in, int Hin, int Win, int C, const int* yidx, const int* xidx, int Hout,
                      int Wout, unsigned char* out, void* stream);
+/* Stage-2 pseudo target (dataset/ReferDataset.py:178-186: `(mask*1.0).sum(0)` as an 'F' image, resized with Image.NEAREST):
+ * masks uint8 [K][Hin][Win] of 0/1 -> out[y][x] = sum_k masks[k][yidx[y]][xidx[x]] as uint8 [Hout][Wout] (index < 0 -> 0),
+ * with the index tables of tris_gather2d_u8.  0 <= K <= 255; K = 0 writes zeros (masks may then be NULL). */
+int tris_mask_sum_nearest_u8(const unsigned char* masks, int K, int Hin, int Win, const int* yidx, const int* xidx,
+                             int Hout, int Wout, unsigned char* out, void* stream);
 /* batch assembly: out[b] = lut[c][cache[index[b]][p][c]]  (to_tensor + normalize, dataset/transform.py:41-53, with the
  * 3x256 float table computed by the host with the reference's float ops).  cache: uint8 [N][HW][3]; index: int64[B];
  * out: fp32 [B][HW][3] (planar=0, channels-last) or [B][3][HW] (planar=1, the reference's NCHW).  HW % 4 == 0. */

@@ -3,6 +3,7 @@
 //   * resample_*: Pillow's two-pass antialiased resampling of 8-bit images (fixed point, 22 fraction bits, intermediate
 //     image rounded to uint8 between the passes) with host-built coefficient tables  -> dataset/transform.py:29 (F.resize)
 //   * gather2d:   Pillow's NEAREST resize (host-built source index tables)            -> dataset/transform.py:32
+//   * mask_sum_nearest: the Stage-2 pseudo target, sum of a ref's instance masks NEAREST-resized -> dataset/ReferDataset.py:178-186
 //   * u8_gather_normalize: to_tensor (/255) + normalize ((x-mean)/std) through a 3x256 table built by the host with the
 //     reference's own float ops, written channels-last (or planar)                    -> dataset/transform.py:41-53
 //   * gather_rows: token-id rows of the sampled sentences                               -> dataset/ReferDataset.py:172-229
@@ -52,6 +53,27 @@ __global__ __launch_bounds__(256) void gather2d_kernel(const unsigned char* __re
   const int xo = (int)(p % Wout), yo = (int)(p / Wout);
   const int ys = yidx[yo], xs = xidx[xo];
   out[i] = (ys < 0 || xs < 0) ? (unsigned char)0 : in[((long)ys * Win + xs) * C + c];
+}
+
+// Stage-2 pseudo target: masks [K][Hin][Win] of 0/1 bytes -> out[y][x] = sum_k masks[k][yidx[y]][xidx[x]].  One thread per
+// output pixel, the K planes walked with one stride; only the K*Hout*Wout bytes the resize keeps are read.  K <= 255
+// (host-checked), so the 32-bit sum of 0/1 bytes fits the byte it is stored as.
+__global__ __launch_bounds__(256) void mask_sum_nearest_kernel(const unsigned char* __restrict__ masks, int K, int Hin,
+                                                               int Win, const int* __restrict__ yidx,
+                                                               const int* __restrict__ xidx, int Hout, int Wout,
+                                                               unsigned char* __restrict__ out) {
+  const long n = (long)Hout * Wout;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int xo = (int)(i % Wout), yo = (int)(i / Wout);
+  const int ys = yidx[yo], xs = xidx[xo];
+  unsigned s = 0;
+  if (ys >= 0 && xs >= 0 && ys < Hin && xs < Win) {
+    const long plane = (long)Hin * Win;
+    const unsigned char* src = masks + (long)ys * Win + xs;
+    for (int k = 0; k < K; ++k) s += src[k * plane];
+  }
+  out[i] = (unsigned char)s;
 }
 
 // cache [N][HW][3] uint8 -> out fp32, one thread per 4 pixels (12 bytes in as three dwords, 48 bytes out).
@@ -135,6 +157,16 @@ extern "C" int tris_gather2d_u8(const unsigned char* in, int Hin, int Win, int C
   if (n <= 0) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(gather2d_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, in, Win, C, yidx, xidx,
                      Hout, Wout, out);
+  TRIS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tris_mask_sum_nearest_u8(const unsigned char* masks, int K, int Hin, int Win, const int* yidx,
+                                        const int* xidx, int Hout, int Wout, unsigned char* out, void* stream) {
+  const long n = (long)Hout * Wout;
+  if (n <= 0 || K < 0 || K > 255 || Hin <= 0 || Win <= 0 || (K > 0 && masks == nullptr)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(mask_sum_nearest_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, masks, K, Hin, Win,
+                     yidx, xidx, Hout, Wout, out);
   TRIS_LAUNCH_CHECK();
   return 0;
 }

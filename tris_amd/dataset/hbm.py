@@ -8,14 +8,23 @@ HBM: the whole dataset, decoded and resized ONCE to the network resolution, is a
   build  (once):  PIL decode on the host -> uint8 to the GPU -> Pillow-exact antialiased resize (tris_resample_u8)
                   into images[n_img, S, S, 3];  masks -> Pillow-exact NEAREST (tris_gather2d_u8) into targets[n_ref, S, S]
                   (training) or kept at their original sizes in one flat buffer (evaluation);  token rows of every
-                  sentence into tokens[n_sent, L].
+                  sentence into tokens[n_sent, L].  Stage-2 training (`pseudo_path` set, not eval_mode): the [K,h,w] bool
+                  stack of every ref's pseudo-mask file is uploaded as it is and summed + NEAREST-resized in one pass
+                  (tris_mask_sum_nearest_u8) into pseudo[n_ref, S, S] -- ReferDataset.load_pseudo, once per run.
   batch  (per step):  the host draws the sentence / negatives of each sample with the reference's own
                   np.random.choice sequence (ReferDataset.sample_text), ships ONE small int64 index vector, and three
                   gather kernels assemble the batch: images are normalised through a 3x256 table straight into the
                   channels-last fp32 layout the stem convolution reads (no NCHW->NHWC pass).
 
 Batches carry the reference's keys, shapes and dtypes (what default_collate makes of ReferDataset samples), so
-train_one_epoch / validate take either loader.
+train_one_epoch / validate take either loader.  A cache with `pseudo` adds targets["pseudo_gt"] (int64 [B,1,S,S]) to its
+training batches, gathered by the same ref index vector as "target".
+
+Evaluation datasets never read pseudo files, whatever their `pseudo_path`: the reference hands its evaluation datasets the
+same directory (validate.py:64), their items carry no pseudo target, and files for those refs do not exist.
+
+`images_from=`: a second cache over the same images at the same size (the train split evaluated after Stage-2 training)
+takes the decoded and resized images of the first instead of decoding them again.
 """
 import os
 
@@ -26,22 +35,61 @@ from .. import ops
 from .transform import normalize_table
 
 
+def _pseudo_file(ds, index):
+    """the pseudo-mask file of training item `index` (dataset/ReferDataset.py:180); FileNotFoundError naming it if it is missing"""
+    path = os.path.join(ds.pseudo_path, f"{index}_{ds.image_record(index)[1]}.npy")
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"pseudo mask file {path} of training item {index} does not exist")
+    return path
+
+
+def _load_pseudo_stack(ds, index):
+    """-> (the bool [K,h,w] instance masks of training item `index`, viewed as uint8; the file's path)"""
+    path = _pseudo_file(ds, index)
+    mask = np.asarray(np.load(path, allow_pickle=True).item()["mask"])
+    if mask.dtype != np.bool_:
+        raise TypeError(f"{path}: 'mask' is {mask.dtype}, expected bool (what make_ins_seg and IRNet write)")
+    if mask.ndim != 3 or mask.shape[1] == 0 or mask.shape[2] == 0:
+        raise ValueError(f"{path}: 'mask' has shape {mask.shape}, expected [K,h,w]")
+    return np.ascontiguousarray(mask).view(np.uint8), path
+
+
 class HbmReferCache:
-    def __init__(self, dataset, size, device="cuda"):
+    """images_from: another cache of the same size whose `images` are reused for every image id it holds.  When it holds all
+    of them the tensor itself is shared; otherwise the missing ones are decoded and appended to a private tensor behind a
+    device copy of the donor's.  Nothing else is shared."""
+
+    def __init__(self, dataset, size, device="cuda", images_from=None):
         if not torch.cuda.is_available():
             raise ops.NoGpuError("HbmReferCache needs the GPU (the CPU path is DataLoader(ReferDataset))")
         self.dataset, self.size, self.device = dataset, size, torch.device(device)
         ds, S, dev = dataset, size, self.device
         n = len(ds)
-        slot = {}
+        donor = images_from
+        if donor is not None and (donor.size != S or donor.device != dev):
+            raise ValueError(f"images_from: a cache of size {donor.size} on {donor.device} cannot serve size {S} on {dev}")
+        slot = dict(donor.slot_by_img) if donor is not None else {}
+        n_donor = len(slot)
         self.slot_of = np.empty(n, np.int64)
         recs = [ds.image_record(i) for i in range(n)]
         for i, (_, img_id, _) in enumerate(recs):
             self.slot_of[i] = slot.setdefault(img_id, len(slot))
-        self.images = torch.empty(len(slot), S, S, 3, dtype=torch.uint8, device=dev)
+        self.slot_by_img = slot           # image id -> row of `images`
+        self.images_shared = donor is not None and len(slot) == n_donor
+        if self.images_shared:
+            self.images = donor.images
+        else:
+            self.images = torch.empty(len(slot), S, S, 3, dtype=torch.uint8, device=dev)
+            if n_donor:
+                self.images[:n_donor].copy_(donor.images)
         self.lut = normalize_table().to(dev)
         train = not ds.eval_mode
         self.targets = torch.empty(n, S, S, dtype=torch.uint8, device=dev) if train else None
+        # Stage-2 pseudo targets: training items only (evaluation items carry none and have no files)
+        with_pseudo = train and getattr(ds, "pseudo_path", None) is not None
+        for i in range(n if with_pseudo else 0):
+            _pseudo_file(ds, i)           # (a missing file stops the build here, before anything is decoded)
+        self.pseudo = torch.empty(n, S, S, dtype=torch.uint8, device=dev) if with_pseudo else None
         self.eval_targets = []            # evaluation: masks at their original sizes
         boxes, paths, sizes, self.files = [], [], [], []
         # decode (once per image) and mask rasterisation (once per ref) on a few host threads -- Pillow releases the
@@ -49,7 +97,8 @@ class HbmReferCache:
         from concurrent.futures import ThreadPoolExecutor
         first_ref = {}
         for i in range(n):
-            first_ref.setdefault(int(self.slot_of[i]), i)
+            if self.slot_of[i] >= n_donor:      # (rows below n_donor are the donor's: already decoded)
+                first_ref.setdefault(int(self.slot_of[i]), i)
         with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
             for s, img in zip(first_ref, pool.map(ds.load_image, first_ref.values())):
                 ops.resample_u8(torch.from_numpy(np.asarray(img).copy()).to(dev), S, S, out=self.images[s])
@@ -65,6 +114,14 @@ class HbmReferCache:
                 sizes.append((h, w))
                 paths.append(int(fname.split(".")[0].split("_")[-1]))
                 self.files.append(fname)
+            # (in chunks: a full-size [K,h,w] stack per ref is many times the cache row it becomes, so the readers must
+            # not run a whole split ahead of the uploads)
+            for a in range(0, n if with_pseudo else 0, 256):
+                chunk = range(a, min(a + 256, n))
+                for i, (stack, path) in zip(chunk, pool.map(lambda j: _load_pseudo_stack(ds, j), chunk)):
+                    if stack.shape[0] > 255:
+                        raise ValueError(f"{path}: {stack.shape[0]} masks, their sum does not fit the uint8 cache")
+                    ops.mask_sum_nearest_u8(torch.from_numpy(stack).to(dev), S, S, out=self.pseudo[i])
         self.boxes = torch.from_numpy(np.stack(boxes).astype(np.int64)).to(dev)
         self.orig_size = torch.from_numpy(np.array(sizes, np.int64)).to(dev)
         self.img_path = torch.tensor(paths, dtype=torch.int64, device=dev).view(-1, 1)
@@ -84,9 +141,12 @@ class HbmReferCache:
         self.token_masks = mrows.contiguous().to(dev)
 
     def nbytes(self):
-        t = self.images.numel() + self.tokens.numel() * self.tokens.element_size()
+        """device bytes this cache owns (images shared through images_from belong to the other cache)"""
+        t = (0 if self.images_shared else self.images.numel()) + self.tokens.numel() * self.tokens.element_size()
         if self.targets is not None:
             t += self.targets.numel()
+        if self.pseudo is not None:
+            t += self.pseudo.numel()
         return t + sum(m.numel() for m in self.eval_targets)
 
 
@@ -152,6 +212,8 @@ class HbmLoader:
             "orig_size": ops.gather_rows(c.orig_size, ref),
             "img_path_full": [c.files[i] for i in indices],
         }
+        if c.pseudo is not None:      # Stage-2 (ReferDataset.load_pseudo)
+            targets["pseudo_gt"] = ops.gather_rows(c.pseudo.view(-1, S * S), ref).view(B, 1, S, S).to(torch.int64)
         return samples, targets
 
     # ---- evaluation: one ref, all its sentences ---------------------------------------------------------------------

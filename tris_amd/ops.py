@@ -2899,6 +2899,29 @@ def resize_nearest_u8(img, out_h, out_w, out=None):
     return out
 
 
+def mask_sum_nearest_u8(masks, out_h, out_w, out=None):
+    """Stage-2 pseudo target of one ref (dataset/ReferDataset.py:178-186): masks uint8 [K,h,w] of 0/1 (a bool stack viewed as
+    uint8) -> uint8 [out_h,out_w] = Pillow NEAREST resize of `masks.sum(0)`; K = 0 gives zeros.  K <= 255: the sum is a byte."""
+    if masks.dim() != 3:
+        raise ValueError(f"expected a [K,h,w] stack, got shape {tuple(masks.shape)}")
+    K, H, W = masks.shape
+    if K > 255:
+        raise ValueError(f"{K} masks in one stack: their sum does not fit the uint8 target (at most 255)")
+    _chk_u8(masks)
+    if H <= 0 or W <= 0 or out_h <= 0 or out_w <= 0:
+        raise ValueError(f"empty image: [{H},{W}] -> [{out_h},{out_w}]")
+    masks = masks.contiguous()
+    if out is None:
+        out = torch.empty(out_h, out_w, dtype=torch.uint8, device=masks.device)
+    else:
+        _chk_u8(out)
+        assert out.shape == (out_h, out_w) and out.is_contiguous()
+    yi, = _pil_tables("nearest", H, out_h, masks.device)
+    xi, = _pil_tables("nearest", W, out_w, masks.device)
+    call("tris_mask_sum_nearest_u8", P(masks) if K else None, K, H, W, P(yi), P(xi), out_h, out_w, P(out), _stream())
+    return out
+
+
 def gather_normalize(cache, index, lut, planar=False):
     """cache uint8 [N,H,W,3], index int64 [B], lut float32 [3,256] -> float32 batch of ToTensor+Normalize'd images:
     planar=False: memory [B,H,W,3], returned as the [B,3,H,W] channels-last view;  planar=True: contiguous [B,3,H,W]."""

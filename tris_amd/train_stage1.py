@@ -262,9 +262,10 @@ def build_dataset(args, split, train, eval_mode, tokenizer=None):
                         tokenizer=tokenizer)
 
 
-def build_loader(args, dataset, batch_size, shuffle, distributed):
+def build_loader(args, dataset, batch_size, shuffle, distributed, images_from=None):
     """The HBM-resident loader (tris_amd.dataset.hbm) by default; TRIS_HBM_LOADER=0 selects the reference's
-    DataLoader(num_workers=2, pin_memory=True) over the same dataset."""
+    DataLoader(num_workers=2, pin_memory=True) over the same dataset.  images_from: a loader built here earlier over the
+    same images (another view of the split); the new cache reuses its decoded images (a DataLoader has none: ignored)."""
     sampler = None
     if distributed:
         if getattr(dataset, "eval_mode", False):
@@ -278,8 +279,8 @@ def build_loader(args, dataset, batch_size, shuffle, distributed):
             sampler = DistributedSampler(dataset, shuffle=shuffle)
     if cfg.hbm_loader:
         from .dataset.hbm import HbmLoader, HbmReferCache
-        return HbmLoader(HbmReferCache(dataset, args.size), batch_size=batch_size, sampler=sampler,
-                         shuffle=shuffle and sampler is None)
+        return HbmLoader(HbmReferCache(dataset, args.size, images_from=getattr(images_from, "cache", None)),
+                         batch_size=batch_size, sampler=sampler, shuffle=shuffle and sampler is None)
     from torch.utils.data import DataLoader
     return DataLoader(dataset, batch_size=batch_size, num_workers=2, pin_memory=True, sampler=sampler,
                       shuffle=shuffle and sampler is None)

@@ -6,6 +6,11 @@ and the final evaluation of the train split with the best checkpoint (:229-247).
 
     python -m tris_amd.train_stage2 --pseudo_path <dir> <the reference's flags>
 
+Batches come from the HBM-resident loader (tris_amd.dataset.hbm; TRIS_HBM_LOADER=0: the reference's DataLoader): images,
+targets and the pseudo masks -- each file summed and NEAREST-resized on the GPU once, when the cache is built -- are gathered on
+the device per step.  The final evaluation of the train split reuses the training cache's images, so the split is decoded and
+resized once per run.
+
 Single GPU, eager steps (the reference's Stage-2 script is single-GPU: --distributed raises).  EMA consistency training
 (--model_ema) needs `ema_pytorch`, which is not on this stack: it raises.  The aux ViT-B/32 the reference loads (:170) is never
 used without EMA and is not loaded.
@@ -78,7 +83,6 @@ def build_dataset(args, split, train, eval_mode, pseudo_path=None, tokenizer=Non
 def main(args, tokenizer=None):
     """tokenizer: as train_stage1.main (an extension; default the CLIP tokenizer)"""
     _check_args(args)
-    from torch.utils.data import DataLoader
     from .model.model_stage2 import TRIS
     from .optim import FusedAdamW
     from .utils.util import load_checkpoint, load_pretrained_checkpoint, save_checkpoint
@@ -114,8 +118,10 @@ def main(args, tokenizer=None):
         raise ValueError("Stage-2 training needs --pseudo_path (the directory of the pseudo masks)")
     train_set = build_dataset(args, "train", train=True, eval_mode=False, pseudo_path=args.pseudo_path,
                               tokenizer=tokenizer)
-    # the reference's DataLoader path (pseudo masks are not part of the HBM cache)
-    train_loader = DataLoader(train_set, batch_size=args.batch_size, num_workers=2, pin_memory=True, shuffle=True)
+    train_loader = build_loader(args, train_set, args.batch_size, True, False)
+    cache = getattr(train_loader, "cache", None)
+    log.info(f"training batches from {type(train_loader).__name__}"
+             + (f": {len(train_set)} refs, {cache.nbytes() / 2 ** 20:.1f} MiB resident, pseudo masks included" if cache is not None else ""))
     steps_total = max(len(train_loader) * args.epoch, 1)
     scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lambda x: (1 - x / steps_total) ** 0.9)
     if args.resume:
@@ -153,7 +159,7 @@ def main(args, tokenizer=None):
         print("loading ", best["path"])
         load_pretrained_checkpoint(best["path"], model)
         train_eval = build_loader(args, build_dataset(args, "train", train=False, eval_mode=True, tokenizer=tokenizer), 1, False,
-                                   False)
+                                  False, images_from=train_loader)
         oIoU, mIoU, hit = evaluate([train_eval])[0]
         print("Validat on the train split: ", oIoU, mIoU, hit)
     print(best)
