@@ -701,6 +701,36 @@ int tris_irn_head_f32(const float* X, long ldx, const float* w, const float* bia
  * E [2][h][w], D [2][h][w][2] */
 int tris_irn_net_finish_f32(const float* E, const float* D, float* edge, float* dp, int h, int w, void* stream);
 
+/* ---- IRNet affinity / displacement training losses (csrc/irnloss.hip; irn_loss.py) -----------------------------------------
+ * The loss head of IRNet/step_refer/train_irn.py ("train_irn.py") on AffinityDisplacementLoss of IRNet/net/resnet50_irn.py
+ * ("irn.py"), with the pair labels of GetAffinityLabelFromIndices (IRNet/voc12/dataloader.py, "dataloader.py", dataloader.py:83-109)
+ * derived from the label map in the kernel.
+ * edge_out [B,1,h,w] logits, dp_out [B,2,h,w], label uint8 [B,h,w]; r = radius - 1 <= 15, h >= r + 1, w >= 2r + 1.  Pairs:
+ * source (y, x) with y < h - r, r <= x < w - r, destination source + dirs[d] (irn.py:183-199, indexing.py:58-88); tables as for
+ * tris_irn_affinity_f32 (n_cells = rows of path_cells).  fp64 arithmetic on the fp32 inputs; integer adds only: every launch is
+ * bitwise reproducible. */
+/* bytes of the partials buffer of tris_irn_loss_fwd_f32 (5 fp64 sums and 3 integer counts per 16 x 16 tile of source pixels);
+ * 0 for a shape the op refuses */
+long tris_irn_loss_workspace_bytes(int B, int h, int w, int radius);
+/* irn.py:168-181 to_affinity (index_select + max_pool2d over the path cells), irn.py:211-220 (pos = -log(aff + 1e-5), neg =
+ * -log(1 + 1e-5 - aff), |pair_disp - (dy, dx)|, |pair_disp|), dataloader.py:97-106 (bg_pos / fg_pos / neg from the labels of the
+ * two ends, both < 21) and train_irn.py:57-63: losses[4] = {bg_pos / 2 + fg_pos / 2, neg, dp_fg, dp_bg}, each sum over its class
+ * divided by N + 1e-5 (2 N + 1e-5 for the two-channel dp terms); counts[3] = {N_bg, N_fg, N_neg}.  norm[5] = the five scales,
+ * kept on the device for the backward.  arg_count int32 [B,3,h,w] (NULL when no backward follows): per class, the pairs whose
+ * path maximum is at the cell; among equal maxima the first cell in the reference's path order (indexing.py:48) takes the pair,
+ * as max_pool2d's backward does.  workspace: tris_irn_loss_workspace_bytes. */
+int tris_irn_loss_fwd_f32(const float* edge_out, const float* dp_out, const unsigned char* label, int B, int h, int w, int radius,
+                          const int* dirs, const int* path_off, const int* path_cells, int n_dirs, int n_cells, float* losses,
+                          long* counts, double* norm, int* arg_count, void* workspace, void* stream);
+/* total_loss.backward() of train_irn.py:68-71 down to edge_out and dp_out: g = DEVICE gradient of losses[4], no host sync.
+ * d_edge[q] = s (1 - s) (g0 (norm0 n_bg + norm1 n_fg) / (1 - s + 1e-5) - g1 norm2 n_neg / (s + 1e-5)) with s = sigmoid(edge_out[q])
+ * and n_* = arg_count at q; d_dp[q] = g2 norm3 (sum of sign(pair_disp - (dy, dx)) over the fg pairs q is the source of, minus
+ * that over the pairs it is the destination of) + g3 norm4 (the same with sign(pair_disp) over the bg pairs); sign(0) = 0.
+ * d_edge / d_dp may be NULL (not wanted). */
+int tris_irn_loss_bwd_f32(const float* edge_out, const float* dp_out, const unsigned char* label, int B, int h, int w, int radius,
+                          const int* dirs, int n_dirs, const int* arg_count, const double* norm, const float* g, float* d_edge,
+                          float* d_dp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

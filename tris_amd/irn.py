@@ -7,7 +7,7 @@ can switch by importing this module:
     rw = irn.propagate_to_edge(instance_cam, edge, beta=10, exp_times=8, radius=5)
 
 (response map, edge map, displacement field) come in as arrays; the edge / displacement network that produces the last two is
-tris_amd.irn_net (inference; its training is not on this stack: INTEGRATION.md, "Stage 2").  numpy inputs are moved to the GPU and numpy comes back; CUDA tensors stay tensors, except
+tris_amd.irn_net (inference; of its training only the losses are on this stack, tris_amd.irn_loss: INTEGRATION.md, "Stage 2").  numpy inputs are moved to the GPU and numpy comes back; CUDA tensors stay tensors, except
 that detect_instance and make_ins_seg always return the reference's dict of numpy arrays.  There is
 no CPU path: without a GPU every function raises ops.NoGpuError.
 

@@ -3379,3 +3379,100 @@ def bn_frozen(x, mean, invstd, gamma, beta, resid=None, relu=False):
     call("tris_bn_apply_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(None if resid is None else resid.contiguous()), P(y),
          x.numel() // C, C, int(relu), _stream())
     return y
+
+
+# ------------------------------------------------------------------------- IRNet affinity / displacement losses (training)
+# csrc/irnloss.hip; the public functions are in tris_amd/irn_loss.py
+_IRN_TABLE_RADIUS = {}
+
+
+def _irn_table_radius(dirs, path_off, path_cells):
+    """radius the tables were built for (max |offset| + 1), after one host check per table set that they are what the kernels index
+    by: dy >= 0, path_off an ascending [D+1] into path_cells, every cell inside its direction's bounding box"""
+    key = (dirs.data_ptr(), path_off.data_ptr(), path_cells.data_ptr(), dirs.shape[0], path_cells.shape[0])
+    r = _IRN_TABLE_RADIUS.get(key)
+    if r is None:
+        d, o, c = dirs.cpu().numpy(), path_off.cpu().numpy(), path_cells.cpu().numpy()
+        D = d.shape[0]
+        ok = d.ndim == 2 and d.shape[1] == 2 and D >= 1 and o.shape == (D + 1,) and c.ndim == 2 and c.shape[1] == 2
+        ok = ok and o[0] == 0 and o[-1] == c.shape[0] and (o[1:] > o[:-1]).all() and (d[:, 0] >= 0).all()
+        if ok:
+            own = d.repeat(o[1:] - o[:-1], axis=0)                 # the direction of every cell
+            ok = ((c[:, 0] >= 0) & (c[:, 0] <= own[:, 0]) & (c[:, 1] >= own[:, 1].clip(max=0)) & (c[:, 1] <= own[:, 1].clip(min=0))).all()
+        if not ok:
+            raise ValueError(f"irn_aff_losses: dirs {tuple(dirs.shape)}, path_off {tuple(path_off.shape)}, path_cells "
+                             f"{tuple(path_cells.shape)} are not the tables of irn.device_tables")
+        r = _IRN_TABLE_RADIUS[key] = int(abs(d).max()) + 1
+    return r
+
+
+def irn_loss_check(edge_out, dp_out, label, radius):
+    """-> (B, h, w); ValueError naming the shapes for what the op does not take"""
+    what = (f"edge_out {tuple(edge_out.shape)} {edge_out.dtype}, dp_out {tuple(dp_out.shape)} {dp_out.dtype}, "
+            f"label {tuple(label.shape)} {label.dtype}")
+    if edge_out.dim() != 4 or dp_out.dim() != 4 or label.dim() != 3:
+        raise ValueError(f"irn_aff_losses takes edge_out [B,1,h,w], dp_out [B,2,h,w], label [B,h,w]; got {what}")
+    B, _, h, w = edge_out.shape
+    if tuple(edge_out.shape) != (B, 1, h, w) or tuple(dp_out.shape) != (B, 2, h, w) or tuple(label.shape) != (B, h, w) or B < 1:
+        raise ValueError(f"irn_aff_losses takes edge_out [B,1,h,w], dp_out [B,2,h,w], label [B,h,w]; got {what}")
+    if edge_out.dtype != torch.float32 or dp_out.dtype != torch.float32 or label.dtype != torch.uint8:
+        raise ValueError(f"irn_aff_losses takes float32 maps and a uint8 label; got {what}")
+    r = int(radius) - 1
+    if r < 1 or r > 15:
+        raise ValueError(f"irn_aff_losses: radius {radius} (2 .. 16)")
+    if h < r + 1 or w < 2 * r + 1:
+        raise ValueError(f"irn_aff_losses: a [{h},{w}] map has no source pixel at radius {radius} (needs h >= {r + 1}, w >= {2 * r + 1}); "
+                         f"got {what}")
+    return B, h, w
+
+
+class IrnAffLossFn(torch.autograd.Function):
+    """AffinityDisplacementLoss.forward's four loss maps (IRNet/net/resnet50_irn.py:211-222) reduced as train_irn.py:57-63 does,
+    with the pair labels of voc12/dataloader.py:90-109 taken from `label` in the kernel: -> (losses[4], counts int64 [3])"""
+
+    @staticmethod
+    def forward(ctx, edge_out, dp_out, label, dirs, path_off, path_cells, radius):
+        B, h, w = irn_loss_check(edge_out, dp_out, label, radius)
+        edge_out, dp_out = _chk_t(edge_out, torch.float32), _chk_t(dp_out, torch.float32)
+        label = _chk_t(label, torch.uint8)
+        dirs, path_off, path_cells = (_chk_t(t, torch.int32) for t in (dirs, path_off, path_cells))
+        if _irn_table_radius(dirs, path_off, path_cells) != radius:
+            raise ValueError(f"irn_aff_losses: the tables are not those of radius {radius}")
+        dev = edge_out.device
+        losses = torch.empty(4, dtype=torch.float32, device=dev)
+        counts = torch.empty(3, dtype=torch.int64, device=dev)
+        norm = torch.empty(5, dtype=torch.float64, device=dev)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        arg_count = torch.empty(B, 3, h, w, dtype=torch.int32, device=dev) if need else None   # (the launch zeroes it)
+        ws = workspace(query("tris_irn_loss_workspace_bytes", B, h, w, radius))
+        call("tris_irn_loss_fwd_f32", P(edge_out), P(dp_out), P(label), B, h, w, radius, P(dirs), P(path_off), P(path_cells),
+             dirs.shape[0], path_cells.shape[0], P(losses), P(counts), P(norm), P(arg_count), P(ws), _stream())
+        ctx.radius = radius
+        if need:
+            ctx.save_for_backward(edge_out, dp_out, label, dirs, arg_count, norm)
+        ctx.mark_non_differentiable(counts)
+        return losses, counts
+
+    @staticmethod
+    def backward(ctx, g, _g_counts):
+        edge_out, dp_out, label, dirs, arg_count, norm = ctx.saved_tensors
+        B, _, h, w = edge_out.shape
+        g = g.to(torch.float32).contiguous()
+        d_edge = torch.empty_like(edge_out) if ctx.needs_input_grad[0] else None
+        d_dp = torch.empty_like(dp_out) if ctx.needs_input_grad[1] else None
+        call("tris_irn_loss_bwd_f32", P(edge_out), P(dp_out), P(label), B, h, w, ctx.radius, P(dirs), dirs.shape[0], P(arg_count),
+             P(norm), P(g), P(d_edge), P(d_dp), _stream())
+        return d_edge, d_dp, None, None, None, None, None
+
+
+def irn_aff_losses(edge_out, dp_out, label, dirs, path_off, path_cells, radius=None):
+    """edge_out [B,1,h,w] logits, dp_out [B,2,h,w], label uint8 [B,h,w] at the maps' size, tables of irn.device_tables(device, radius)
+    -> (losses[4] = (pos_aff, neg_aff, dp_fg, dp_bg), counts int64 [3] = (N_bg, N_fg, N_neg)), differentiable in the two maps.
+    radius: what the tables were built for; None reads it from the tables (one device-to-host copy per table set)."""
+    for t in (edge_out, dp_out, label, dirs, path_off, path_cells):
+        if not t.is_cuda:
+            irn_loss_check(edge_out, dp_out, label, 2 if radius is None else radius)
+            raise NoGpuError("tris_amd ops run on MI355X only (got a CPU tensor); there is no CPU fallback")
+    if radius is None:
+        radius = _irn_table_radius(*(_chk_t(t, torch.int32) for t in (dirs, path_off, path_cells)))
+    return IrnAffLossFn.apply(edge_out, dp_out, label, dirs, path_off, path_cells, int(radius))
