@@ -48,9 +48,9 @@ int tris_gemm_f32(const float* A, const float* B, float* C, int M, int N, int K,
 int tris_gemm_epilogue_next(float* pre_out, const float* dact_x);
 
 /* One-shot: the NEXT tris_gemm_f32 launched from the calling thread may finish a split-K product INSIDE its own launch: each tile's
- * k slices take a ticket from tickets[tile], and the block that arrives last sums the tile's slabs in slice order (the result is
+ * k slices take a ticket from tickets[tile], and the block that arrives last sums the tile's slabs in the order of the reduce launch it replaces (the result is
  * the separate reduce launch's, bit for bit, whichever block that is), applies bias / activation / residual and writes C.  Used for
- * up to 8 slices (developer option FUSE_SPLITK = n, 0 = never), one batch, the fast kernels.  `tickets`: `count` ints in device
+ * up to 16 slices (developer option FUSE_SPLITK = n, 0 = never), one batch, the fast kernels.  `tickets`: `count` ints in device
  * memory, ZERO when handed over; every launch leaves them zero; private to the stream of the launch (two products in flight at
  * once must not share an array; a captured launch keeps reading the same array at every replay).  Without it, or with fewer ints
  * than the product has tiles, the slabs are summed by a second launch.  (The small products of the transformer towers and of the

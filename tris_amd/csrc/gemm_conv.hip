@@ -33,7 +33,7 @@ __attribute__((visibility("hidden"))) int tris_internal_xcd_order = -1;
 __attribute__((visibility("hidden"))) int tris_internal_red_grid = 0;
 // FUSE_SPLITK: largest slice count whose slabs are summed by the last-arriving block of each tile inside the product's own launch
 // (gemm_fast.h "fused split-K finish"; needs tris_splitk_tickets_next); 0 = always the separate reduce launch
-__attribute__((visibility("hidden"))) int tris_internal_fuse_splitk = 8;
+__attribute__((visibility("hidden"))) int tris_internal_fuse_splitk = 16;   // (= TRIS_FUSE_SPLITK_DEFAULT, gemm_params.h)
 __attribute__((visibility("hidden"))) long tris_internal_fused_count = 0;
 // option that lives in xattn_px.hip's translation unit
 extern __attribute__((visibility("hidden"))) int tris_internal_xattn_px_slots;

@@ -489,17 +489,21 @@ int run_cfg(GemmParams p, int batch, float* ws, hipStream_t st, Cfg cfg, int mod
   // fused split-K finish (gemm_fast.h): the fast kernels, one batch, few slices, an armed ticket array with a slot per tile
   int* const tk = p.tickets;
   p.tickets = nullptr;
-  // (not where the wide reduce kernel would run -- many slices of a small output: its summation order differs, and the fused finish
-  //  is to be the separate launch's result bit for bit: static-tile runs and their tests see no change in arithmetic)
+  // The fused finish is to be the separate launch's result bit for bit (static-tile runs and their tests see no change in
+  // arithmetic): where the wide reduce kernel would run -- many slices of a small output -- it sums the slabs in THAT kernel's order
+  // (p.fin_groups; the vector form of the finish only, otherwise the two launches stay).
   const bool wide = (p.N & 3) == 0 && al16(ws) && al16(Cfinal) && splitk >= 8 && (long)p.M * p.N / 4 < 128 * 256 && tris_internal_reduce_wide;
+  const bool vec_fin = (p.N % 4 == 0) && al16(Cfinal) && (p.ldc % 4 == 0) && (!p.resid || (al16(p.resid) && p.ldr % 4 == 0)) &&
+                       (p.bias_mode != 1 || al16(p.bias));
   const bool fuse = splitk > 1 && splitk <= tris_internal_fuse_splitk && splitk <= TRIS_FUSE_SPLITK_MAX && tk != nullptr && fast &&
-                    batch == 1 && tiles_m * tiles_n <= p.tickets_n && !wide;
+                    batch == 1 && tiles_m * tiles_n <= p.tickets_n && (!wide || vec_fin);
+  p.fin_groups = 0;
   if (fuse) {
     __atomic_fetch_add(&tris_internal_fused_count, 1L, __ATOMIC_RELAXED);
     p.tickets = tk;
     p.Cfin = Cfinal;
-    p.vecCfin = (p.N % 4 == 0) && al16(Cfinal) && (p.ldc % 4 == 0) && (!p.resid || (al16(p.resid) && p.ldr % 4 == 0)) &&
-                (p.bias_mode != 1 || al16(p.bias));
+    p.vecCfin = vec_fin;
+    if (wide) p.fin_groups = tris_internal_reduce_wide >= 16 ? 16 : tris_internal_reduce_wide >= 8 ? 8 : 4;
   }
   if (splitk > 1)
     p.vecC = (p.N % 4 == 0) && al16(ws);

@@ -1144,9 +1144,10 @@ void gemm_fast_kernel(GemmParams p) {
       o[p.N + n0 + tid] = q;
     }
   }
-  // ---- fused split-K finish (EPI_SLAB, p.tickets != NULL: run_cfg, S <= 8 slices) ------------------------------------------------
+  // ---- fused split-K finish (EPI_SLAB, p.tickets != NULL: run_cfg, S <= TRIS_FUSE_SPLITK_MAX slices) ------------------------------------------------
   // The slab of this block is in the workspace.  Every block of a tile takes a ticket; the LAST arriver sums the tile's S slabs in
-  // the fixed order s = 0 .. S - 1 (the order of splitk_reduce_kernel: the result does not depend on who arrives last, and equals
+  // the fixed order s = 0 .. S - 1 (the order of splitk_reduce_kernel; p.fin_groups: the order of the wide reduce kernel, where the
+  // separate launch would be that one: the result does not depend on who arrives last, and equals
   // the separate reduce launch bit for bit), applies the standard epilogue and stores C -- one launch instead of two for the ~190
   // small split-K products of a step.  Hand-off (MI355X_MICROARCH.md, inter-workgroup visibility): plain
   // stores -> every wave waits for its own stores -> barrier -> one lane: agent-scope release (writes the XCD's L2 back), wait,
@@ -1184,6 +1185,26 @@ void gemm_fast_kernel(GemmParams p) {
           const long idx = (long)row * p.N + col;
           float v[4] = {0.f, 0.f, 0.f, 0.f};
           int s2 = 0;
+          if (p.fin_groups > 0) {   // (uniform) the order of splitk_reduce_wide_kernel<G>: group g sums slabs g, g + G, ..; then the groups
+            const int G = p.fin_groups;
+            for (int g = 0; g < G; ++g) {
+              float a[4] = {0.f, 0.f, 0.f, 0.f};
+              int s3 = g;
+              for (; s3 + 3 * G < S; s3 += 4 * G) {
+                const float4 x0 = ld4(slab + (long)s3 * total + idx), x1 = ld4(slab + (long)(s3 + G) * total + idx);
+                const float4 x2 = ld4(slab + (long)(s3 + 2 * G) * total + idx), x3 = ld4(slab + (long)(s3 + 3 * G) * total + idx);
+                a[0] = (((a[0] + x0.x) + x1.x) + x2.x) + x3.x; a[1] = (((a[1] + x0.y) + x1.y) + x2.y) + x3.y;
+                a[2] = (((a[2] + x0.z) + x1.z) + x2.z) + x3.z; a[3] = (((a[3] + x0.w) + x1.w) + x2.w) + x3.w;
+              }
+              for (; s3 < S; s3 += G) {
+                const float4 x0 = ld4(slab + (long)s3 * total + idx);
+                a[0] += x0.x; a[1] += x0.y; a[2] += x0.z; a[3] += x0.w;
+              }
+#pragma unroll
+              for (int t = 0; t < 4; ++t) v[t] = g == 0 ? a[t] : v[t] + a[t];
+            }
+            s2 = S;
+          }
           for (; s2 + 3 < S; s2 += 4) {   // (four slabs in flight per trip; the additions in slice order)
             const float4 a = ld4(slab + (long)s2 * total + idx), b = ld4(slab + (long)(s2 + 1) * total + idx);
             const float4 c = ld4(slab + (long)(s2 + 2) * total + idx), d = ld4(slab + (long)(s2 + 3) * total + idx);

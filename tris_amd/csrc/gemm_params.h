@@ -69,9 +69,11 @@ struct GemmParams {
   int tickets_n;    // (host: capacity of the armed array; run_cfg keeps `tickets` only where the fused form is launched)
   float* Cfin;
   int vecCfin;      // 16-byte stores / loads legal for Cfin, the residual and the bias
+  int fin_groups;   // fused finish: 0 = slabs summed in slice order (splitk_reduce_kernel's); G > 0 = in the order of
+                    // splitk_reduce_wide_kernel<G> (G interleaved groups, then the groups), where the separate launch would be that kernel
 };
-#define TRIS_FUSE_SPLITK_MAX 8
-#define TRIS_FUSE_SPLITK_DEFAULT 8
+#define TRIS_FUSE_SPLITK_MAX 16
+#define TRIS_FUSE_SPLITK_DEFAULT 16
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 typedef float gp_f32x4 __attribute__((ext_vector_type(4)));

@@ -63,11 +63,13 @@ class GraphedFrozenText:
     GEMM autotuner has seen every shape), replayed as ONE launch per step on the caller's side stream.  The output is a static
     buffer: consume it before the next replay (the step's own stream order guarantees that)."""
 
-    def __init__(self, clip_model, n, L, warmup=2):
+    def __init__(self, clip_model, n, L, warmup=2, ids=None):
         dev = next(clip_model.parameters()).device
         self.s_ids = torch.zeros(n, L, device=dev, dtype=torch.int64)
         self.s_ids[:, 0] = 49406
         self.s_ids[:, L - 1] = 49407      # (full-length sentences: the warm-up calls -- and the autotuner behind them -- see every row in use)
+        if ids is not None:               # (tests: record on these token ids instead -- the recording must not depend on them)
+            self.s_ids.copy_(ids)
         from . import ops
         # (h2 products tag their operands with words of a PER-STEP amax pool: a graph that outlives the step must not hold such
         # pointers -- this tower owns its words, cleared inside the graph; its frozen weights have constant words)

@@ -532,10 +532,15 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, tA, tB, batch=1, sA=0, sB=0, sC=0, bia
         C.reshape(M, N).copy_(C4[:M])
         return C
     ws = workspace(0) if (use_ws and batch == 1 and not _BATCH_INVARIANT) else None   # (no workspace = no split-K)
+    blind = _rows_limit_blind(A, tA, batch)
     if (w_b and batch == 1 and not tA and M >= cfg.gemm_convert and cfg.gemm_convert > 0 and K % 32 == 0 and lda == K and getattr(B, "_tris_linear_w", False)
-            and planes_on() and pl_word(A) is None and A.is_contiguous() and A.data_ptr() % 16 == 0 and _pl_weight_ok(B)):
+            and planes_on() and pl_word(A) is None and A.is_contiguous() and A.data_ptr() % 16 == 0 and _pl_weight_ok(B) and not blind):
         A = _a_planes(A, M, K)
-    pA, pB = h2_pp(A, B, w_a=w_a, w_b=w_b, k_red=K, w_bt=w_bt and not tB) if batch == 1 else (P(A), P(B))
+    if blind:
+        PL_STATS["last"] = PL_STATS["last_t"] = False
+        pA, pB = P(A), P(unplanes(B))
+    else:
+        pA, pB = h2_pp(A, B, w_a=w_a, w_b=w_b, k_red=K, w_bt=w_bt and not tB) if batch == 1 else (P(A), P(B))
     if batch == 1 and PL_STATS["last_t"]:    # B = W [K][N] arrived as the planes of its transpose [N][K]
         tB, ldb = True, K
     if mark:
@@ -2234,10 +2239,23 @@ class rows_limit:
 
     def __enter__(self):
         call("tris_rows_limit_thread", self.ptr)
+        _TLS.rows_limit = self.ptr      # (ops.gemm: no amax pre-pass over an operand whose rows behind the limit may hold anything)
 
     def __exit__(self, *exc):
+        _TLS.rows_limit = None
         call("tris_rows_limit_thread", None)
         return False
+
+
+def _rows_limit_blind(A, tA, batch):
+    """A row limit is live, the product obeys it (row-major A, one batch) and A carries no amax word of this step: the h2 pre-pass
+    (tris_amax_bits_f32 over ALL of A) would read the rows behind the limit, which a packed pass never writes -- torch.empty
+    memory, possibly NaN or huge -- into the scale of the rows in use.  Such a product runs in x3 (no data-dependent scale); its
+    output is tagged by its own launch, so the next product is back in h2.  CLIP.encode_text_hidden never gets here: every A of the
+    packed pass is written by the launch right before the product that reads it and tagged there (LayerNorm, attention, product),
+    over the rows in use only; this guards callers of ops.gemm that bring an operand of their own under ops.rows_limit."""
+    return (getattr(_TLS, "rows_limit", None) is not None and batch == 1 and not tA and h2_on() and pl_word(A) is None
+            and _h2_tag_slot(A) is None)
 
 
 def packed_rows(N, L):
