@@ -731,6 +731,35 @@ int tris_irn_loss_bwd_f32(const float* edge_out, const float* dp_out, const unsi
                           const int* dirs, int n_dirs, const int* arg_count, const double* norm, const float* g, float* d_edge,
                           float* d_dp, void* stream);
 
+/* ---- IRNet edge / displacement heads, training (csrc/irntrain.hip, csrc/irnnet.hip, csrc/optim.hip; irn_train.py) ------------
+ * What IRNet/step_refer/train_irn.py:55-72 needs below the loss head: the trunk is frozen and its taps detached (irn.py:117-121,
+ * :145-147), so only fc_edge1..6 and fc_dp1..7 have a backward.  fp64 block partials summed in index order, no atomics: every
+ * launch is bitwise reproducible. */
+/* stage1 up to the ReLU (resnet50.py:61-64) on a batch of normalised float images, as the training loader delivers them
+ * (dataloader.py:249-256 pads with zeros AFTER the normalisation, which no uint8 + table input can express):
+ * img [B][H][W][3] -> Y [B][Ho][Wo][64], no flip row; the same kernel body and arithmetic as tris_irn_stem_f32. */
+int tris_irn_stem_batch_f32(const float* img, const float* Wk, const float* mean, const float* invstd, const float* gamma,
+                            const float* beta, float* Y, int B, int H, int W, void* stream);
+/* autograd's backward of nn.GroupNorm -> nn.Upsample(scale) -> [..., :Ho, :Wo] -> nn.ReLU (irn.py:29-96, :125-137): the adjoint of
+ * tris_gn_apply_up_f32 with relu = 1.  dY / Y: gradient and forward output in the concatenation buffer (pixel pitch ldy, both
+ * pointers already at the slice's first channel; the mask is Y > 0); T [B][Hi][Wi][C] the GroupNorm input; stats as
+ * tris_gn_stats_f32 left them.  dT [B][Hi][Wi][C] = gradient of T; dU (may be NULL): the gradient of the GroupNorm OUTPUT, before
+ * the norm's own backward; dgamma, dbeta [C].  scale = 1 | 2 | 4.  workspace: tris_gn_up_bwd_workspace_bytes. */
+long tris_gn_up_bwd_workspace_bytes(int B, long HW, int C, int G);
+int tris_gn_up_bwd_f32(const float* dY, const float* Y, long ldy, const float* T, const float* stats, const float* gamma, float* dT,
+                       float* dU, float* dgamma, float* dbeta, int B, int Hi, int Wi, int C, int G, int scale, int Ho, int Wo,
+                       void* workspace, void* stream);
+/* backward of tris_irn_head_f32 (fc_edge6, irn.py:57; fc_dp7's last convolution, :97): g [M][N] the gradient of Y;
+ * dX[m][c] = sum_n g[m][n] w[n][c] (pitch C), dw[n][c] = sum_m g[m][n] X[m*ldx + c], db[n] = sum_m g[m][n] (db may be NULL).
+ * N = 1 | 2, C % 32 == 0, C <= 256.  workspace: tris_irn_head_bwd_workspace_bytes. */
+long tris_irn_head_bwd_workspace_bytes(long M, int C, int N);
+int tris_irn_head_bwd_f32(const float* g, const float* X, long ldx, const float* w, float* dX, float* dw, float* db, long M, int C,
+                          int N, void* workspace, void* stream);
+/* one step of torch.optim.SGD as PolyOptimizer drives it (IRNet/misc/torchutils.py:9-31) over a flat arena: g = grad + wd p;
+ * buf = g when first != 0, else momentum buf + g; p -= lr buf.  The poly schedule of lr is the host's. */
+int tris_sgd_momentum_f32(float* p, const float* g, float* buf, long n, float lr, float momentum, float weight_decay, int first,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

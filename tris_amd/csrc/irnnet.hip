@@ -12,24 +12,19 @@
 #include "common.h"
 #include "tris_hip.h"
 #include "bilinear.h"
+#include "irn_gn.h"
 
 namespace {
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-inline int ew_grid(long n) {
-  long g = (n + 255) / 256;
-  return (int)(g < 8192 ? (g < 1 ? 1 : g) : 8192);
-}
 
 // ------------------------------------------------------------------------------------------------------------------ stem
 constexpr int ST = 16;                 // output tile edge: 256 threads, one output pixel (64 channels) each
 constexpr int SP = 2 * ST + 5;         // input patch edge
 constexpr int SPW = SP * 3 + 1;        // patch row pitch in floats
 
-// img uint8 [H][W][3]; lut [3][256]; Wk [7][7][3][64]; Y [2][Ho][Wo][64], row 1 = the image flipped along W
-__global__ __launch_bounds__(256) void irn_stem_kernel(const unsigned char* __restrict__ img, const float* __restrict__ lut,
+// T = unsigned char: img uint8 [H][W][3]; lut [3][256]; Y [2][Ho][Wo][64], row 1 = the image flipped along W.
+// T = float: img [B][H][W][3], already normalised (lut unused); Y [B][Ho][Wo][64], no flip row.  Wk [7][7][3][64].
+template <typename T>
+__global__ __launch_bounds__(256) void irn_stem_kernel(const T* __restrict__ img, const float* __restrict__ lut,
                                                        const float* __restrict__ Wk, const float* __restrict__ mean,
                                                        const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, float* __restrict__ Y, int H, int W,
@@ -45,10 +40,17 @@ __global__ __launch_bounds__(256) void irn_stem_kernel(const unsigned char* __re
     const int iy = iy0 + py, ix = ix0 + px;
     float v0 = 0.f, v1 = 0.f, v2 = 0.f;
     if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
-      const unsigned char* p = img + ((long)iy * W + (b ? W - 1 - ix : ix)) * 3;
-      v0 = lut[p[0]];
-      v1 = lut[256 + p[1]];
-      v2 = lut[512 + p[2]];
+      if constexpr (sizeof(T) == 1) {
+        const unsigned char* p = img + ((long)iy * W + (b ? W - 1 - ix : ix)) * 3;
+        v0 = lut[p[0]];
+        v1 = lut[256 + p[1]];
+        v2 = lut[512 + p[2]];
+      } else {
+        const float* p = img + (((long)b * H + iy) * W + ix) * 3;
+        v0 = p[0];
+        v1 = p[1];
+        v2 = p[2];
+      }
     }
     float* d = sp + py * SPW + px * 3;
     d[0] = v0; d[1] = v1; d[2] = v2;
@@ -137,13 +139,6 @@ __global__ __launch_bounds__(256) void subsample2_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------------------ GroupNorm
-constexpr int GN_BLOCKS = 256;   // row blocks per image at most (fixed for a shape: the sums are reproducible)
-
-inline int gn_blocks(long HW) {
-  long nb = (HW + 63) / 64;
-  return (int)(nb < GN_BLOCKS ? (nb < 1 ? 1 : nb) : GN_BLOCKS);
-}
-
 // part[((b * nblk + blk) * G + g) * 2] = {sum, sum of squares} of the block's rows, fp64.  256 threads = RS rows x CV channel vectors.
 __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict__ X, long HW, int C, int G, long rpb,
                                                          double* __restrict__ part) {
@@ -309,8 +304,18 @@ int tris_irn_stem_f32(const unsigned char* img, const float* lut, const float* W
                       const float* gamma, const float* beta, float* Y, int H, int W, void* stream) {
   if (H < 1 || W < 1) return (int)hipErrorInvalidValue;
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-  hipLaunchKernelGGL(irn_stem_kernel, dim3(cdiv(Wo, ST), cdiv(Ho, ST), 2), dim3(256), 0, (hipStream_t)stream, img, lut, Wk, mean,
-                     invstd, gamma, beta, Y, H, W, Ho, Wo);
+  hipLaunchKernelGGL(irn_stem_kernel<unsigned char>, dim3(cdiv(Wo, ST), cdiv(Ho, ST), 2), dim3(256), 0, (hipStream_t)stream, img, lut,
+                     Wk, mean, invstd, gamma, beta, Y, H, W, Ho, Wo);
+  TRIS_LAUNCH_CHECK();
+  return 0;
+}
+
+int tris_irn_stem_batch_f32(const float* img, const float* Wk, const float* mean, const float* invstd, const float* gamma,
+                            const float* beta, float* Y, int B, int H, int W, void* stream) {
+  if (B < 1 || B > 65535 || H < 1 || W < 1) return (int)hipErrorInvalidValue;
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  hipLaunchKernelGGL(irn_stem_kernel<float>, dim3(cdiv(Wo, ST), cdiv(Ho, ST), B), dim3(256), 0, (hipStream_t)stream, img,
+                     (const float*)nullptr, Wk, mean, invstd, gamma, beta, Y, H, W, Ho, Wo);
   TRIS_LAUNCH_CHECK();
   return 0;
 }
@@ -331,10 +336,6 @@ int tris_subsample2_f32(const float* X, float* Y, int B, int H, int W, int C, vo
                      W, Ho, Wo, C / 4);
   TRIS_LAUNCH_CHECK();
   return 0;
-}
-
-static bool gn_shape_ok(int C, int G) {
-  return C >= 4 && C <= 1024 && C % 4 == 0 && 256 % (C / 4) == 0 && G >= 1 && G <= 256 && C % G == 0 && (C / G) % 4 == 0;
 }
 
 long tris_gn_workspace_bytes(int B, long HW, int G) { return (long)B * gn_blocks(HW) * G * 2 * (long)sizeof(double); }

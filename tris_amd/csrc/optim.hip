@@ -67,6 +67,33 @@ __global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, c
     v[j] = V;
   }
 }
+// SGD with momentum and weight decay over one flat arena, torch.optim.SGD's update (dampening 0, no Nesterov) as the reference's
+// PolyOptimizer steps it (IRNet/misc/torchutils.py:9-31): g = grad + wd p;  buf = g on the first step, else mom buf + g;  p -= lr buf.
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long n,
+                                                  float lr, float mom, float wd, int first) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long n4 = n >> 2;
+  for (long j = i; j < n4; j += stride) {
+    float4 P = *reinterpret_cast<float4*>(p + j * 4), G = *reinterpret_cast<const float4*>(g + j * 4);
+    float4 M = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!first) M = *reinterpret_cast<float4*>(buf + j * 4);
+#define TRIS_SGD1(e)                                \
+  G.e = G.e + wd * P.e;                             \
+  M.e = first ? G.e : mom * M.e + G.e;              \
+  P.e -= lr * M.e;
+    TRIS_SGD1(x) TRIS_SGD1(y) TRIS_SGD1(z) TRIS_SGD1(w)
+#undef TRIS_SGD1
+    *reinterpret_cast<float4*>(p + j * 4) = P;
+    *reinterpret_cast<float4*>(buf + j * 4) = M;
+  }
+  for (long j = n4 * 4 + i; j < n; j += stride) {
+    const float G = g[j] + wd * p[j];
+    const float M = first ? G : mom * buf[j] + G;
+    p[j] -= lr * M;
+    buf[j] = M;
+  }
+}
 }  // namespace
 
 // step_count is the 1-based step index t; bias corrections are computed on the host in double.
@@ -91,6 +118,19 @@ extern "C" int tris_adamw_dev_f32(float* p, const float* g, float* m, float* v, 
   if (g4 < 1) g4 = 1;
   hipLaunchKernelGGL(adamw_dev_kernel, dim3((unsigned)g4), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, hyper, beta1,
                      beta2, eps, weight_decay);
+  TRIS_LAUNCH_CHECK();
+  return 0;
+}
+
+// first != 0: the momentum buffer is written, not read (torch creates it as a copy of the first gradient)
+extern "C" int tris_sgd_momentum_f32(float* p, const float* g, float* buf, long n, float lr, float momentum, float weight_decay,
+                                     int first, void* stream) {
+  if (n < 1 || !p || !g || !buf) return (int)hipErrorInvalidValue;
+  long g4 = (n / 4 + 255) / 256;
+  if (g4 > 8192) g4 = 8192;
+  if (g4 < 1) g4 = 1;
+  hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)g4), dim3(256), 0, (hipStream_t)stream, p, g, buf, n, lr, momentum, weight_decay,
+                     first);
   TRIS_LAUNCH_CHECK();
   return 0;
 }

@@ -8,7 +8,7 @@ IRNet/step_refer/train_irn.py on AffinityDisplacementLoss (IRNet/net/resnet50_ir
 edge_out [B,1,h,w] (logits) and dp_out [B,2,h,w] are what the network's two heads return in train mode (MeanShift is the identity
 there); label is the uint8 class map at the maps' size, from which the kernel derives the pair labels the reference's
 GetAffinityLabelFromIndices builds on the host (IRNet/voc12/dataloader.py:83-109).  Nothing per pair is ever in memory
-("IRNet training losses").  The backward of the heads and the optimiser are not on this stack ("Stage 2").
+("IRNet training losses").  The backward of the heads and the optimiser are tris_amd.irn_train.
 There is no CPU path: CPU tensors raise ops.NoGpuError.
 """
 import numpy as np

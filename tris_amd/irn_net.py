@@ -8,8 +8,8 @@ The module is a holder of parameters and buffers under the reference's names (IR
 the computation is HIP kernels on channels-last activations: the ResNet-50 trunk's 1x1 and 3x3 products on the MFMA paths
 (ops.linear, ops.conv3x3), frozen BatchNorm as tris_bn_apply_f32 with an invstd formed once at load time, and the stem, pooling,
 GroupNorm / upsample / concatenation, narrow heads and flip-average of csrc/irnnet.hip.  Both flip rows go through the network as
-one B = 2 batch.  There is no CPU path: without a GPU forward raises ops.NoGpuError.  Training the network and the CRF labels it
-trains on are not on this stack.
+one B = 2 batch.  There is no CPU path: without a GPU forward raises ops.NoGpuError.  Training the two branches is
+tris_amd.irn_train; the CRF labels it trains on are not on this stack.
 
 In the h2 arithmetic the products read fp32 activations and split them in their own loops (operand planes are a training-step
 construct: they are not used here).  The products take the cost model's tile choice (ops.autotune_off): image sizes change from

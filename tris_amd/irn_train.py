@@ -1,0 +1,136 @@
+"""Training IRNet's edge / displacement heads on the MI355X: the loop body of the reference's IRNet/step_refer/train_irn.py:55-72 and
+its closing mean-shift pass (:93-106) on this stack.
+
+    net = EdgeDisplacement(); net.load_state_dict(backbone_and_initial_heads); net.cuda()
+    trainer = IrnTrainer(net, lr=0.1, weight_decay=1e-4, max_step=n_steps)
+    for img, label in batches:                       # img float32 [B,3,H,W] normalised, label uint8 [B,H,W] (or at the maps' size)
+        out = trainer.train_step(img, label)         # {'losses' [4], 'total', 'counts' [3]}: device tensors, no host sync
+    trainer.fit_mean_shift(eval_batches)
+    torch.save(trainer.state_dict(), path)           # the file `python -m tris_amd.make_ins_seg --irn_weights_name` takes
+
+The reference detaches every trunk tap (IRNet/net/resnet50_irn.py:117-121) and keeps the backbone in eval mode (:145-147): the
+ResNet-50 runs forward only, under no_grad, on the inference kernels of tris_amd.irn_net behind a float stem; fc_edge1..6 and
+fc_dp1..7 train (ops.IrnHeadsFn, csrc/irntrain.hip), the loss is tris_amd.irn_loss, the optimiser tris_amd.optim.PolySGD.
+Train-mode semantics: MeanShift is the identity (:111-114), there is no flip-average.  There is no CPU path: ops.NoGpuError.
+Not here: the dataset and its augmentation, a command line, the CRF labels, data parallelism, graph capture.
+"""
+import contextlib
+
+import torch
+
+from . import irn_loss, ops
+from .irn_net import EDGE, DP, EdgeDisplacement
+from .optim import PolySGD
+
+
+def head_parameter_names():
+    """(edge names, dp names): the reference's trainable_parameters() (resnet50_irn.py:141-143), canonical names in its order"""
+    edge = [f"fc_edge{i + 1}.{s}" for i in range(len(EDGE)) for s in ("0.weight", "1.weight", "1.bias")]
+    edge += ["fc_edge6.weight", "fc_edge6.bias"]
+    dp = [f"fc_dp{i + 1}.{s}" for i in range(len(DP)) for s in ("0.weight", "1.weight", "1.bias")]
+    dp += ["fc_dp7.0.weight", "fc_dp7.1.weight", "fc_dp7.1.bias", "fc_dp7.3.weight"]
+    return edge, dp
+
+
+class IrnTrainer:
+    """IrnTrainer(net, lr, weight_decay, max_step, radius=10): the reference's two parameter groups (edge at 1 x lr, dp at 10 x lr,
+    train_irn.py:32-36) become trainable, everything else stays frozen."""
+
+    def __init__(self, net, lr, weight_decay, max_step, radius=10):
+        if not isinstance(net, EdgeDisplacement):
+            raise TypeError(f"IrnTrainer takes a tris_amd.irn_net.EdgeDisplacement, got {type(net).__name__}")
+        self.net, self.radius = net, int(radius)
+        named = dict(net.named_parameters())
+        edge, dp = head_parameter_names()
+        for p in named.values():
+            p.requires_grad_(False)
+        self.edge_params = [named[k].requires_grad_(True) for k in edge]
+        self.dp_params = [named[k].requires_grad_(True) for k in dp]
+        self.optimizer = PolySGD([{"params": self.edge_params, "lr": 1 * lr, "weight_decay": weight_decay},
+                                  {"params": self.dp_params, "lr": 10 * lr, "weight_decay": weight_decay}],
+                                 lr=lr, weight_decay=weight_decay, max_step=max_step)
+        net._prep = None       # (the parameters moved into the optimiser's arenas: the load-time views are formed again)
+
+    # ------------------------------------------------------------------------------------------------------------- pieces
+    @contextlib.contextmanager
+    def scope(self, explicit=False):
+        """what every pass over the network runs inside -- train_step, eval_outputs, and a caller of the pieces taps() / heads():
+        the cost model's tile choice (image sizes change from batch to batch) and one h2 step (ops.h2_step)"""
+        with ops.autotune_off(), ops.h2_step(explicit):
+            yield
+
+    def _input(self, img):
+        if not isinstance(img, torch.Tensor) or img.dtype != torch.float32 or img.dim() != 4 or 3 not in (img.shape[1], img.shape[3]):
+            what = f"{tuple(img.shape)} {img.dtype}" if isinstance(img, torch.Tensor) else type(img).__name__
+            raise ValueError(f"IrnTrainer takes a float32 image batch [B,3,H,W] or [B,H,W,3], got {what}")
+        dev = self.net.fc_edge6.weight.device
+        if not torch.cuda.is_available() or dev.type != "cuda":
+            raise ops.NoGpuError("tris_amd.irn_train runs on MI355X only (move the network to the GPU); there is no CPU fallback")
+        img = img.to(dev)
+        if img.shape[3] != 3:
+            img = img.permute(0, 2, 3, 1)
+        return img.contiguous()
+
+    @torch.no_grad()
+    def taps(self, img):
+        """the frozen trunk on a normalised float batch -> [x1 .. x5], channels-last"""
+        net = self.net
+        img = self._input(img)
+        p = net._prepare(img.device)
+        r = net.resnet50
+        y = ops.irn_stem_batch(img, p["stem_w"], r.bn1.running_mean, p["inv"][r.bn1], r.bn1.weight, r.bn1.bias)
+        return net._trunk(ops.maxpool3s2(y))
+
+    def heads(self, taps, keep=None):
+        """the two branches in train mode -> (edge_out [B,1,h,w], dp_out [B,2,h,w]), differentiable in the head parameters"""
+        return ops.irn_heads(taps, self.edge_params + self.dp_params, keep)
+
+    def _label(self, label, hw):
+        if not isinstance(label, torch.Tensor) or label.dtype != torch.uint8 or label.dim() != 3:
+            what = f"{tuple(label.shape)} {label.dtype}" if isinstance(label, torch.Tensor) else type(label).__name__
+            raise ValueError(f"IrnTrainer.train_step takes a uint8 label [B,H,W], got {what}")
+        label = label.to(self.net.fc_edge6.weight.device)
+        if tuple(label.shape[1:]) != tuple(hw):
+            label = irn_loss.reduce_label(label)
+            if tuple(label.shape[1:]) != tuple(hw):
+                raise ValueError(f"IrnTrainer.train_step: the label reduces to {tuple(label.shape[1:])}, the maps are {tuple(hw)}")
+        return label.contiguous()
+
+    # --------------------------------------------------------------------------------------------------------------- step
+    def train_step(self, img, label):
+        """one iteration of train_irn.py:55-72 -> {'losses' [4] = (pos_aff, neg_aff, dp_fg, dp_bg), 'total', 'counts' int64 [3]},
+        detached device tensors (no host sync)"""
+        img = self._input(img)
+        with self.scope(explicit=True):      # one amax pool for the step; the arenas' weights get their amaxes at its start
+            taps = self.taps(img)
+            edge_out, dp_out = self.heads(taps)
+            label = self._label(label, edge_out.shape[2:])
+            losses, counts = irn_loss.affinity_displacement_losses(edge_out, dp_out, label, self.radius)
+            total = irn_loss.total_loss(losses)
+            self.optimizer.zero_grad()
+            total.backward()
+            self.optimizer.step()
+        return {"losses": losses.detach(), "total": total.detach(), "counts": counts}
+
+    # --------------------------------------------------------------------------------------------------------- mean shift
+    @torch.no_grad()
+    def eval_outputs(self, img):
+        """the eval-mode batched forward, model(img, False) of train_irn.py:102: (edge_out [B,1,h,w], dp_out [B,2,h,w]) with the
+        current mean shift subtracted (resnet50_irn.py:114)"""
+        img = self._input(img)
+        with self.scope():
+            edge_out, dp_out = self.heads(self.taps(img))
+        return edge_out, dp_out - self.net.mean_shift.running_mean.view(1, 2, 1, 1)
+
+    @torch.no_grad()
+    def fit_mean_shift(self, batches):
+        """train_irn.py:93-106: mean(dp, dim=(0, 2, 3)) of every batch, their mean -> mean_shift.running_mean; returns it"""
+        means = [torch.mean(self.eval_outputs(img)[1], dim=(0, 2, 3)) for img in batches]
+        if not means:
+            raise ValueError("fit_mean_shift: no batches")
+        self.net.mean_shift.running_mean.copy_(torch.mean(torch.stack(means), dim=0))
+        return self.net.mean_shift.running_mean
+
+    def state_dict(self):
+        """the network's tensors under canonical names, on the CPU: what EdgeDisplacement.load_state_dict loads"""
+        return {k: v.detach().cpu().clone() for k, v in self.net.state_dict().items()}

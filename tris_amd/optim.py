@@ -18,7 +18,7 @@ ALIGN = 64  # floats (256 B)
 
 
 class Arena:
-    def __init__(self, params):
+    def __init__(self, params, moments=2):
         self.params = [p for p in params if p.requires_grad and not getattr(p, "_tris_no_grad_path", False)]
         dev = self.params[0].device
         offs, n = [], 0
@@ -29,7 +29,7 @@ class Arena:
         self.p = torch.zeros(n, device=dev, dtype=torch.float32)
         self.g = torch.zeros(n, device=dev, dtype=torch.float32)
         self.m = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.v = torch.zeros(n, device=dev, dtype=torch.float32)
+        self.v = torch.zeros(n, device=dev, dtype=torch.float32) if moments > 1 else None   # (SGD keeps one buffer)
         self.offsets = offs
         for p, o in zip(self.params, offs):
             pv, gv = self._view(self.p, p, o), self._view(self.g, p, o)
@@ -225,3 +225,93 @@ class FusedAdamW(torch.optim.Optimizer):
             # parameters joined training at different times, which the Stage-1 recipe never does.
             raise ValueError(f"per-parameter step counts differ ({sorted(steps)}): not representable by the fused AdamW")
         self._steps = steps.pop() if steps else 0
+
+
+class PolySGD(torch.optim.Optimizer):
+    """The reference's PolyOptimizer (IRNet/misc/torchutils.py:9-31) as one fused launch per parameter group over flat arenas.
+
+    It reproduces what the reference DOES.  PolyOptimizer calls `super().__init__(params, lr, weight_decay)`, and the third
+    positional parameter of torch.optim.SGD is `momentum`: the value passed as weight_decay becomes the default MOMENTUM (1e-4 in
+    train_irn.py), and a group's weight decay is whatever its own dict carries (0 if it carries none).  `self.momentum = 0.9` of the
+    reference is only the exponent of the poly schedule (here: `power`).  This is deliberate -- weights trained here follow the
+    reference's trajectory, not the one its argument names suggest.
+
+    Before each step, on the host in Python floats as the reference computes it: lr_i = initial_lr_i (1 - step / max_step) ** power
+    while step < max_step (afterwards the last lr stays).  Update (torch.optim.SGD, dampening 0, no Nesterov): g = grad + wd p;
+    buf = g on the first step, else momentum buf + g; p -= lr buf.  Gradients are read from the arenas' views (p.grad), which the
+    backward kernels write directly."""
+
+    def __init__(self, params, lr, weight_decay, max_step, power=0.9):
+        # the reference's positional call: SGD(params, lr, momentum=<the weight_decay argument>)
+        super().__init__(params, dict(lr=lr, momentum=weight_decay, dampening=0, weight_decay=0, nesterov=False))
+        self.global_step = 0
+        self.max_step = max_step
+        self.power = power
+        for g in self.param_groups:
+            g.setdefault("initial_lr", g["lr"])      # (travels in the group like a torch scheduler's: the schedule survives a reload)
+        self.arenas = [Arena(g["params"], moments=1) for g in self.param_groups]
+        self._has_buf = [False] * len(self.arenas)      # per group: momentum buffers exist (torch creates them at a first step)
+        for a in self.arenas:
+            ops.h2_register_arena(a)
+
+    def scheduled_lr(self):
+        """the learning rates the next step() will use"""
+        if self.global_step < self.max_step:
+            lr_mult = (1 - self.global_step / self.max_step) ** self.power
+            return [g["initial_lr"] * lr_mult for g in self.param_groups]
+        return [g["lr"] for g in self.param_groups]
+
+    def zero_grad(self, set_to_none=False):
+        """nothing to clear: the backward kernels overwrite the arenas' gradients every step"""
+        return None
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if not all(a.p.is_cuda for a in self.arenas):
+            raise ops.NoGpuError("PolySGD steps on the MI355X only (the parameters are on the CPU); there is no CPU fallback")
+        for g, lr in zip(self.param_groups, self.scheduled_lr()):
+            g["lr"] = lr
+        ops.wgrad_join()
+        st = torch.cuda.current_stream().cuda_stream
+        for i, (g, a) in enumerate(zip(self.param_groups, self.arenas)):
+            _lib.call("tris_sgd_momentum_f32", a.p.data_ptr(), a.g.data_ptr(), a.m.data_ptr(), a.numel, float(g["lr"]),
+                      float(g["momentum"]), float(g["weight_decay"]), int(not self._has_buf[i]), st)
+            self._has_buf[i] = True
+        self.global_step += 1
+
+    # ---- checkpoint format: torch.optim.SGD's own layout ({'state': {index: {'momentum_buffer'}}, 'param_groups'}) + 'global_step'
+    def state_dict(self):
+        state, groups, base = {}, [], 0
+        for i, (g, a) in enumerate(zip(self.param_groups, self.arenas)):
+            offs = {id(p): o for p, o in zip(a.params, a.offsets)}
+            if self._has_buf[i]:
+                for j, p in enumerate(g["params"]):
+                    if id(p) in offs:
+                        state[base + j] = {"momentum_buffer": Arena._view(a.m, p, offs[id(p)]).detach().clone()}
+            pg = {k: v for k, v in g.items() if k != "params"}
+            pg["params"] = list(range(base, base + len(g["params"])))
+            groups.append(pg)
+            base += len(g["params"])
+        return {"state": state, "param_groups": groups, "global_step": self.global_step}
+
+    def load_state_dict(self, sd):
+        if len(sd["param_groups"]) != len(self.param_groups):
+            raise ValueError(f"optimizer state has {len(sd['param_groups'])} parameter groups, this optimizer {len(self.param_groups)}")
+        for gi, (g, a, sg) in enumerate(zip(self.param_groups, self.arenas, sd["param_groups"])):
+            if len(sg["params"]) != len(g["params"]):
+                raise ValueError(f"parameter group {gi}: {len(sg['params'])} parameters in the checkpoint, {len(g['params'])} in the model")
+            g.update({k: v for k, v in sg.items() if k != "params"})
+            a.m.zero_()
+            offs = {id(p): o for p, o in zip(a.params, a.offsets)}
+            have = [(p, (sd["state"].get(idx) or {}).get("momentum_buffer")) for p, idx in zip(g["params"], sg["params"]) if id(p) in offs]
+            n = sum(b is not None for _, b in have)
+            if 0 < n < len(have):
+                # one fused launch either creates every buffer of a group or reads every one; torch decides it per parameter
+                raise ValueError(f"parameter group {gi}: {n} of {len(have)} parameters have a momentum buffer: not representable "
+                                 "by the fused SGD")
+            for p, b in have:
+                if b is not None:
+                    with torch.no_grad():
+                        Arena._view(a.m, p, offs[id(p)]).copy_(b.reshape(p.shape))
+            self._has_buf[gi] = n > 0       # (whether the next step reads the buffers follows what was loaded, as in torch)
+        self.global_step = int(sd.get("global_step", 0))
