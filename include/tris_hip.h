@@ -760,6 +760,28 @@ int tris_irn_head_bwd_f32(const float* g, const float* X, long ldx, const float*
 int tris_sgd_momentum_f32(float* p, const float* g, float* buf, long n, float lr, float momentum, float weight_decay, int first,
                           void* stream);
 
+/* ---- IRNet's training input pipeline (csrc/irndata.hip; dataset/irn_data.py) ------------------------------------------------
+ * What ReferAffinityDataset.__getitem__ (IRNet/voc12/dataloader.py:222-285) does per sample on the host, for a whole batch in one
+ * launch from uint8 arenas in HBM: random_scale (IRNet/misc/imutils.py:48-55: Pillow BICUBIC image, NEAREST label), the
+ * normalisation (dataloader.py:67-81) through lut [3][256], random_lr_flip (imutils.py:57-66), random_crop / top_left_crop with
+ * fills 0 / 255 (imutils.py:68-130) and pil_rescale(label, 0.25, 0) (dataloader.py:281).  Bit-exact against Pillow.
+ * desc [B][TRIS_IRN_AUG_DESC] longs: image offset (bytes, a multiple of 16; images [H][W][3]), label offset ([H][W]), H, W, target
+ * H, target W, the box of imutils.py:91 (cont_top, cont_bottom, cont_left, cont_right, img_top, img_bottom, img_left, img_right),
+ * flags (1: horizontal table, 2: vertical table, 4: flipped), taps per column / row entry, and six offsets into `tables` (ints):
+ * column bounds [cw][2] and taps [cw][kh], row bounds [ch][2] and taps [ch][kv], the label's source column [cw] and row [ch], all
+ * in the order of the box's columns and rows.  An axis without a table is not resampled.  The host checks every entry
+ * (irn_data.validate_batch): at most TRIS_IRN_AUG_KMAX taps, at most TRIS_IRN_AUG_PATCH source rows / columns under one
+ * TRIS_IRN_AUG_TILE-wide tile.  The image arena ends in 16 spare bytes.
+ * img [B][crop][crop][3] f32 (what tris_irn_stem_batch_f32 reads), label [B][crop][crop], label_reduced [B][crop/4][crop/4];
+ * crop % 4 == 0.  No atomics: two runs give equal bytes. */
+#define TRIS_IRN_AUG_TILE 32
+#define TRIS_IRN_AUG_PATCH 80
+#define TRIS_IRN_AUG_KMAX 12
+#define TRIS_IRN_AUG_DESC 24
+int tris_irn_augment_batch_u8(const unsigned char* img_arena, const unsigned char* lab_arena, const long* desc, const int* tables,
+                              const float* lut, float* img, unsigned char* label, unsigned char* label_reduced, int B, int crop,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ The reference detaches every trunk tap (IRNet/net/resnet50_irn.py:117-121) and k
 ResNet-50 runs forward only, under no_grad, on the inference kernels of tris_amd.irn_net behind a float stem; fc_edge1..6 and
 fc_dp1..7 train (ops.IrnHeadsFn, csrc/irntrain.hip), the loss is tris_amd.irn_loss, the optimiser tris_amd.optim.PolySGD.
 Train-mode semantics: MeanShift is the identity (:111-114), there is no flip-average.  There is no CPU path: ops.NoGpuError.
-Not here: the dataset and its augmentation, a command line, the CRF labels, data parallelism, graph capture.
+The dataset, its augmentation and the command line: tris_amd.dataset.irn_data, tris_amd.train_irn.
+Not here: the CRF labels, data parallelism, graph capture of the step.
 """
 import contextlib
 

@@ -2976,6 +2976,25 @@ def gather_normalize(cache, index, lut, planar=False):
     return out if planar else out.permute(0, 3, 1, 2)
 
 
+def irn_augment_batch(img_arena, lab_arena, packed, desc_bytes, lut, B, crop):
+    """IRNet's training augmentation of one batch in one launch (dataset/irn_data.py; IRNet/voc12/dataloader.py:222-285): packed =
+    the batch's descriptors (int64 [B, TRIS_IRN_AUG_DESC], desc_bytes of them) followed by its int32 tables, already checked by
+    irn_data.validate_batch -> (img float32 [B,3,crop,crop] as the channels-last view of [B,crop,crop,3], label uint8
+    [B,crop,crop], label_reduced uint8 [B,crop/4,crop/4])."""
+    _chk_u8(img_arena, lab_arena, packed)
+    _chk(lut)
+    if crop % 4 or desc_bytes != B * CONSTS["TRIS_IRN_AUG_DESC"] * 8 or packed.numel() <= desc_bytes:
+        raise ValueError(f"irn_augment_batch: crop {crop}, {desc_bytes} descriptor bytes for a batch of {B}")
+    assert img_arena.is_contiguous() and lab_arena.is_contiguous() and packed.is_contiguous() and lut.shape == (3, 256)
+    dev = img_arena.device
+    img = torch.empty(B, crop, crop, 3, dtype=torch.float32, device=dev)
+    label = torch.empty(B, crop, crop, dtype=torch.uint8, device=dev)
+    reduced = torch.empty(B, crop // 4, crop // 4, dtype=torch.uint8, device=dev)
+    call("tris_irn_augment_batch_u8", P(img_arena), P(lab_arena), P(packed), packed.data_ptr() + desc_bytes, P(lut.contiguous()),
+         P(img), P(label), P(reduced), B, crop, _stream())
+    return img.permute(0, 3, 1, 2), label, reduced
+
+
 def gather_rows(table, index):
     """table [N, ...] (any dtype, row size a multiple of 4 bytes), index int64 [R] -> [R, ...]"""
     if not table.is_cuda:
