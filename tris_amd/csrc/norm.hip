@@ -805,13 +805,15 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ X, float* __restri
   }
 }
 
-// generic column sum for widths that are not a multiple of 4 (rare, small): one thread per column
+// generic column sum for widths / leading dimensions that are not a multiple of 4 or a misaligned X (rare, small): one thread per
+// column.  The sum is kept in fp64 like the partials of the vector path (col_partial_kernel): the accuracy of a bias gradient does
+// not depend on N % 4 (a serial fp32 sum of 4097 rows was 10 - 70 x further from fp64 than the CPU's fp32 sum)
 __global__ void colsum_scalar_kernel(const float* __restrict__ X, long M, int N, long ld, float* __restrict__ out) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= N) return;
-  float s = 0.f;
-  for (long r = 0; r < M; ++r) s += X[r * ld + c];
-  out[c] = s;
+  double s = 0.0;
+  for (long r = 0; r < M; ++r) s += (double)X[r * ld + c];
+  out[c] = (float)s;
 }
 
 inline int grid_for(long n, int block = 256) {
@@ -837,7 +839,7 @@ inline int bn_grid(long n4, int C) {
 
 struct ColPlan { int nb; long rpb; };
 inline ColPlan col_plan(long M, int C) {
-  int CV = C / 4, CVB = CV < 256 ? CV : 256, RS = 256 / CVB;
+  int CV = C >= 4 ? C / 4 : 1, CVB = CV < 256 ? CV : 256, RS = 256 / CVB;   // (C < 4: only tris_colsum_f32's scalar kernel, which uses no workspace)
   const int target = tris_internal_col_blocks;
   long rpb = (M + target - 1) / target;
   long minr = (long)RS * 8;
