@@ -782,6 +782,51 @@ int tris_irn_augment_batch_u8(const unsigned char* img_arena, const unsigned cha
                               const float* lut, float* img, unsigned char* label, unsigned char* label_reduced, int B, int crop,
                               void* stream);
 
+/* ---- IRNet's dense-CRF label pass (csrc/crf.hip; crf.py) ---------------------------------------------------------------------
+ * IRNet/step_refer/cam_to_ir_label.py:45-76 ("cam_to_ir_label.py") and crf_inference_label of IRNet/misc/imutils.py:169-183
+ * ("imutils.py"): DenseCRF2D's mean field (Kraehenbuehl & Koltun 2011) with the Gaussian (imutils.py:178) and bilateral
+ * (imutils.py:179) Potts terms filtered on the permutohedral lattice (Adams, Baek & Davis 2010), as DESIGN.md section 14 states it.
+ * N = H W pixels, d = 2 (Gaussian) | 5 (bilateral) feature dimensions, M lattice vertices, C = 1 | 2 | 4 channels laid out
+ * [N][C] / [M][C].  f32, no atomics: every launch is bitwise reproducible. */
+/* the packed vertex key: d signed coordinates of TRIS_CRF_FIELD_BITS bits each, biased by 2^(bits-1), coordinate 0 in the highest
+ * field; the host refuses an image whose coordinates could leave the field (crf.check_size) */
+#define TRIS_CRF_FIELD_BITS 12
+/* addPairwiseGaussian / addPairwiseBilateral's feature embedding (imutils.py:178-179): per pixel the d+1 enclosing lattice vertices
+ * keys [N][d+1] (packed) and their barycentric weights bary [N][d+1].  tx [W], ty [H], tc [256]: the host's float32 tables x / sxy,
+ * y / sxy, v / srgb; scale [d] = sqrt(2/3) (d+1) / sqrt((i+1)(i+2)) computed in double.  d = 2: features (tx[x], ty[y]), img and tc
+ * unused (NULL); d = 5: (tx[x], ty[y], tc[r], tc[g], tc[b]) of img uint8 [H][W][3].  One rounding per operation, no contraction:
+ * bit-identical to the float32 restatement.  6 H W < 2^31. */
+int tris_crf_lattice_points_f32(const unsigned char* img, const float* tx, const float* ty, const float* tc, const float* scale,
+                                int H, int W, int d, long* keys, float* bary, void* stream);
+/* the blur's neighbour table (imutils.py:181, the lattice behind d.inference): uniq [M] the sorted distinct keys; nbr [d+1][2][M] =
+ * the index of (key - 1 everywhere, + d + 1 at the axis) and of its opposite, found by binary search, -1 where absent */
+int tris_crf_neighbours_i64(const long* uniq, int M, int d, int* nbr, void* stream);
+/* one filter pass K (imutils.py:181, one Potts term of one mean-field iteration): out = norm * alpha * slice(blur(splat(norm * x))),
+ * alpha = 1 / (1 + 2^-d); norm [N] may be NULL (plain K).  inv [N][d+1]: the vertex index of every (pixel, r); order [N (d+1)]: the
+ * (pixel, r) pairs e = p (d+1) + r sorted by vertex, ascending within a vertex; off [M+1]: each vertex's span of `order`.  Splat
+ * is a segmented sum in list order (no float atomics), then the d+1 blur steps, one launch each, then slice.  x and out may be the
+ * same buffer.  workspace: tris_crf_filter_workspace_bytes(M, C). */
+long tris_crf_filter_workspace_bytes(int M, int C);
+int tris_crf_filter_f32(const float* x, float* out, int N, int C, int d, int M, const float* bary, const int* inv,
+                        const int* order, const int* off, const int* nbr, const float* norm, float* workspace, void* stream);
+/* the symmetric normalisation of both terms (imutils.py:178-179, NormalizationType.NORMALIZE_SYMMETRIC, the default):
+ * norm = 1 / sqrt(k1 + 1e-20) with k1 = K 1 */
+int tris_crf_norm_f32(const float* k1, int N, float* norm, void* stream);
+/* cam_to_ir_label.py:51-52, :61-62, :66-67 and unary_from_labels (imutils.py:175): c = cam < 0 ? 0 : cam, label = c > thr (strict:
+ * the argmax of [thr, cam] gives 0 on a tie) for thr_fg and thr_bg; U [N][2 CRFs][2 labels] = e_same where the label agrees else
+ * e_diff (-log(gt_prob), -log(1 - gt_prob) as float32); Q = softmax(-U) */
+int tris_crf_unary_cam_f32(const float* cam, int N, float thr_fg, float thr_bg, float e_same, float e_diff, float* U, float* Q,
+                           void* stream);
+/* the same from R = 1 | 2 given label maps uint8 [R][N] holding 0 / 1 (imutils.py:175 with the caller's labels): U, Q [N][R][2] */
+int tris_crf_unary_labels_u8(const unsigned char* labels, int R, int N, float e_same, float e_diff, float* U, float* Q,
+                             void* stream);
+/* one mean-field update (imutils.py:181): Q = softmax over the two labels of -U + wg g + wb b, the maximum subtracted; g, b the
+ * two filtered terms [N][R][2] */
+int tris_crf_update_f32(const float* U, const float* g, const float* b, float wg, float wb, int N, int R, float* Q, void* stream);
+/* imutils.py:183 and cam_to_ir_label.py:58-74: pred = argmax over the labels (the first on a tie) of both CRFs of Q [N][2][2];
+ * conf = fg_pred; conf[fg_pred == 0] = 255; conf[bg_pred + fg_pred == 0] = 0; out uint8 [N] */
+int tris_crf_combine_u8(const float* Q, int N, unsigned char* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3709,3 +3709,99 @@ def irn_heads(taps, params, keep=None):
     in-place update between forward and backward: do not step in between), and a parameter whose gradient has an arena view gets
     it OVERWRITTEN, not accumulated: a second backward before the optimiser's step replaces the first."""
     return IrnHeadsFn.apply(keep, *taps, *params)
+
+
+# ------------------------------------------------------------------------------------------ dense-CRF label pass (IRNet)
+# csrc/crf.hip; the lattices, the mean field and the functions with the reference's names are in tris_amd/crf.py
+def crf_lattice_points(img, tx, ty, tc, scale, H, W):
+    """per pixel the d+1 lattice vertices and barycentric weights: -> (keys int64 [N,d+1] packed, bary float32 [N,d+1]).
+    d = len(scale) = 2 (features tx[x], ty[y]; img, tc None) | 5 (and tc[r], tc[g], tc[b] of img uint8 [H,W,3])"""
+    tx, ty, scale = (_chk_t(t, torch.float32) for t in (tx, ty, scale))
+    d = scale.numel()
+    if d not in (2, 5) or tx.numel() != W or ty.numel() != H:
+        raise ValueError(f"crf_lattice_points: d={d}, tables {tx.numel()} x {ty.numel()} for an image of {H}x{W}")
+    if d == 5:
+        img, tc = _chk_t(img, torch.uint8), _chk_t(tc, torch.float32)
+        if tuple(img.shape) != (H, W, 3) or tc.numel() != 256:
+            raise ValueError(f"crf_lattice_points: image {tuple(img.shape)}, colour table {tc.numel()}")
+    else:
+        img = tc = None
+    keys = torch.empty(H * W, d + 1, dtype=torch.int64, device=tx.device)
+    bary = torch.empty(H * W, d + 1, dtype=torch.float32, device=tx.device)
+    call("tris_crf_lattice_points_f32", P(img), P(tx), P(ty), P(tc), P(scale), H, W, d, P(keys), P(bary), _stream())
+    return keys, bary
+
+
+def crf_neighbours(uniq, d):
+    """sorted distinct packed keys int64 [M] -> int32 [d+1, 2, M], -1 for an absent neighbour"""
+    uniq = _chk_t(uniq, torch.int64)
+    M = uniq.numel()
+    nbr = torch.empty(d + 1, 2, M, dtype=torch.int32, device=uniq.device)
+    call("tris_crf_neighbours_i64", P(uniq), M, int(d), P(nbr), _stream())
+    return nbr
+
+
+def crf_filter(x, d, bary, inv, order, off, nbr, norm=None):
+    """one permutohedral filter pass: x [N,C] (C = 1 | 2 | 4) -> [N,C] = norm * K(norm * x) (plain K without norm)"""
+    x, bary = _chk_t(x, torch.float32), _chk_t(bary, torch.float32)
+    inv, order, off, nbr = (_chk_t(t, torch.int32) for t in (inv, order, off, nbr))
+    N, C = x.shape
+    M = off.numel() - 1
+    if tuple(bary.shape) != (N, d + 1) or tuple(inv.shape) != (N, d + 1) or order.numel() != N * (d + 1) \
+            or tuple(nbr.shape) != (d + 1, 2, M) or C not in (1, 2, 4):
+        raise ValueError(f"crf_filter: x {tuple(x.shape)}, d={d}, M={M}, bary {tuple(bary.shape)}, nbr {tuple(nbr.shape)}")
+    if norm is not None:
+        norm = _chk_t(norm, torch.float32)
+        if norm.numel() != N:
+            raise ValueError(f"crf_filter: norm of {norm.numel()} for {N} points")
+    out = torch.empty_like(x)
+    ws = workspace(query("tris_crf_filter_workspace_bytes", M, C))
+    call("tris_crf_filter_f32", P(x), P(out), N, C, int(d), M, P(bary), P(inv), P(order), P(off), P(nbr), P(norm), P(ws), _stream())
+    return out
+
+
+def crf_norm(k1):
+    """1 / sqrt(K 1 + 1e-20)"""
+    k1 = _chk_t(k1, torch.float32)
+    out = torch.empty_like(k1)
+    call("tris_crf_norm_f32", P(k1), k1.numel(), P(out), _stream())
+    return out
+
+
+def crf_unary_cam(cam, thr_fg, thr_bg, e_same, e_diff):
+    """cam [H,W] -> (U, Q) [N, 2 CRFs, 2 labels]: negative values are 0, label = cam > thr (strict), Q = softmax(-U)"""
+    cam = _chk_t(cam, torch.float32)
+    N = cam.numel()
+    U = torch.empty(N, 2, 2, dtype=torch.float32, device=cam.device)
+    Q = torch.empty_like(U)
+    call("tris_crf_unary_cam_f32", P(cam), N, float(thr_fg), float(thr_bg), float(e_same), float(e_diff), P(U), P(Q), _stream())
+    return U, Q
+
+
+def crf_unary_labels(labels, e_same, e_diff):
+    """labels uint8 [R,N] of 0 / 1, R = 1 | 2 -> (U, Q) [N, R, 2]"""
+    labels = _chk_t(labels, torch.uint8)
+    R, N = labels.shape
+    if R not in (1, 2):
+        raise ValueError(f"crf_unary_labels: {R} label maps")
+    U = torch.empty(N, R, 2, dtype=torch.float32, device=labels.device)
+    Q = torch.empty_like(U)
+    call("tris_crf_unary_labels_u8", P(labels), R, N, float(e_same), float(e_diff), P(U), P(Q), _stream())
+    return U, Q
+
+
+def crf_update(U, g, b, wg, wb, out=None):
+    """Q = softmax over the labels of -U + wg g + wb b; all [N,R,2]"""
+    U, g, b = (_chk_t(t, torch.float32) for t in (U, g, b))
+    N, R, _ = U.shape
+    Q = torch.empty_like(U) if out is None else out
+    call("tris_crf_update_f32", P(U), P(g), P(b), float(wg), float(wb), N, R, P(Q), _stream())
+    return Q
+
+
+def crf_combine(Q):
+    """Q [N,2,2] -> uint8 [N]: fg_pred, 255 where fg_pred == 0, 0 where bg_pred + fg_pred == 0"""
+    Q = _chk_t(Q, torch.float32)
+    out = torch.empty(Q.shape[0], dtype=torch.uint8, device=Q.device)
+    call("tris_crf_combine_u8", P(Q), Q.shape[0], P(out), _stream())
+    return out

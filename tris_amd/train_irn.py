@@ -14,7 +14,8 @@ the reference's IRNet/step_refer/train_irn.py on this stack.
 
 The argument names are those of IRNet/run_sample_refer.py that train_irn.run reads; --num_workers is accepted and unused (the
 batches come from the HBM cache: tris_amd.dataset.irn_data, where the random numbers are documented).
-Not here: data parallelism, graph capture of the step, the CRF labels.
+The labels come from `python -m tris_amd.cam_to_ir_label`.
+Not here: data parallelism, graph capture of the step.
 """
 import argparse
 import time
