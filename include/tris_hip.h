@@ -618,6 +618,21 @@ int tris_bce4_bwd_f32(const float* x1, const float* x2, const float* x3, const f
  * tris_eval_post_f32 (the arg-max of the raw map) stays the Stage-1 entry.  map: S x S.  workspace >= 2049 + 4*1024 floats. */
 int tris_eval_post_signed_f32(const float* map, int S, const unsigned char* target, int oH, int oW, float* cam, long* out_iu,
                               float* workspace, void* stream);
+/* PointM and the box metrics of one (image, sentence) (csrc/boxes.hip; validate.py:106-117, 191-208, utils/box_eval_utils.py:10-73,
+ * utils/box_utils.py:50-63), DESIGN section 15.  cam [H,W] is the map tris_eval_post*_f32 left, thresholded here at 1e-9; iu its
+ * int64[3] (the arg-max is read from iu[2] on the device); target uint8 [H,W]; gt_box int32[4] (x1, y1, x2, y2), device memory.
+ * generate_bbox on a boolean mask, restated: proposals = bounding rectangles of the 8-connected foreground components and of the
+ * holes (4-connected background components that do not reach the frame) grown by one pixel, ordered by the raster index of each
+ * component's first pixel (the project's tie rule); confidence = foreground share (double); torchvision's CPU NMS at 0.05 on
+ * the (x, y, w, h) rows read as (x1, y1, x2, y2), float32; kept = survivors with confidence > 0.5 * max over all proposals.
+ * record int32[16] = {hitm, proposals, NMS survivors, kept, bbox_hit x1, y1, x2, y2, box_acc, box_miou (float32 bits),
+ * max confidence (float64 bits, low word first), 0, 0, 0, 0}; an all-zero / all-one mask gives the reference's default list:
+ * 0 proposals, 0 kept, bbox_hit = (0, 0, 1, 1).  boxes_out int32 [kept][5] = (x, y, w, h, foreground count) in kept order, room
+ * for H*W + 1 rows.  workspace: tris_eval_boxes_workspace_bytes(H, W) bytes, 8-byte aligned.  H*W <= 2^24 (float32 areas stay
+ * exact), else hipErrorInvalidValue (the size query returns -1). */
+long tris_eval_boxes_workspace_bytes(int H, int W);
+int tris_eval_boxes_f32(const float* cam, const unsigned char* target, int H, int W, const int* gt_box, const long* iu, int* record,
+                        int* boxes_out, void* workspace, void* stream);
 
 /* ---- Instance-mask synthesis (csrc/insseg.hip; irn.py): the post-network half of IRNet's make_ins_seg_labels --------------
  * (response map, edge map [h,w], displacement field [2,h,w]) -> instance masks, the pseudo labels Stage 2 trains on.  Reference

@@ -26,6 +26,7 @@ assigning to it (`cfg.step_graph = "seg"`, `monkeypatch.setattr(cfg, "bn_pool", 
   xattn_h2           TRIS_XATTN_H2             pixel-row launch in the h2 arithmetic inside an h2 step (two fp16 pieces); 0: always split-bf16
   hbm_loader         TRIS_HBM_LOADER           HBM-resident input pipeline (0: the reference's DataLoader)
   eval_group         TRIS_EVAL_GROUP           refs per batched evaluation group
+  eval_boxes         TRIS_EVAL_BOXES           validate also reports HitM / box_mIOU / box_Acc (ops.eval_boxes per sentence; default 0: validate as it was, launch for launch)
   mbox_spin          TRIS_MBOX_SPIN            bound of the SyncBatchNorm mailbox spin (polls)
   syncbn_comm        TRIS_SYNCBN_COMM          "mailbox" | "c10d"
   ddp_check          TRIS_DDP_CHECK            NaN-poison check of the gradient reducer's release order
@@ -89,6 +90,7 @@ class _Config:
         self.xattn_bwd_px = _flag("TRIS_XATTN_BWD_PX", True)
         self.hbm_loader = _flag("TRIS_HBM_LOADER", True)
         self.eval_group = max(1, int(e("TRIS_EVAL_GROUP", "16")))
+        self.eval_boxes = _flag("TRIS_EVAL_BOXES", False)
         self.mbox_spin = int(e("TRIS_MBOX_SPIN", "40000000"))
         self.syncbn_comm = e("TRIS_SYNCBN_COMM", "mailbox")
         self.ddp_check = e("TRIS_DDP_CHECK") == "1"

@@ -3196,6 +3196,62 @@ def eval_post_signed(seg_map, target_u8):
     return iu, cam
 
 
+EVAL_BOXES_RECORD = 16   # int32 words of tris_eval_boxes_f32's record (include/tris_hip.h)
+
+
+def eval_boxes_gt(bbox, device="cuda"):
+    """ground-truth boxes (anything array-like, [..., 4] as x1, y1, x2, y2) -> int32 [K, 4] on the device, the operand of eval_boxes"""
+    b = torch.as_tensor(bbox).reshape(-1, 4)
+    return b.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
+
+
+def decode_boxes_record(words):
+    """the record's 16 int32 words (a list of Python ints, or 8 int64 words) -> dict of its fields"""
+    import numpy as np
+    w = np.asarray(words)
+    w = w.astype(np.int64).view(np.int32) if len(w) == EVAL_BOXES_RECORD // 2 else w.astype(np.int32)
+    return {"hitm": int(w[0]), "n_prop": int(w[1]), "n_nms": int(w[2]), "n_kept": int(w[3]),
+            "bbox_hit": tuple(int(v) for v in w[4:8]), "box_acc": int(w[8]), "box_miou": w[9:10].view(np.float32)[0],
+            "cmax": float(w[10:12].view(np.float64)[0])}
+
+
+def eval_boxes(cam, target_u8, gt_box, iu, return_boxes=False):
+    """PointM and the box metrics of one (image, sentence) (validate.py:106-117, 191-208; utils/box_eval_utils.py:10-73) behind
+    eval_post / eval_post_signed: cam [H,W] and iu int64[3] as they return them, gt_box int32[4] on the device (eval_boxes_gt).
+    -> record int32[16] on the device (decode_boxes_record); with return_boxes (a host sync) -> (record, the reference's list
+    [(x1, y1, x2, y2, conf)] -- the default list for an all-zero / all-one mask)."""
+    _chk(cam, target_u8, iu)
+    if cam.dtype != torch.float32 or target_u8.dtype != torch.uint8 or iu.dtype != torch.int64 or iu.numel() != 3:
+        raise TypeError("eval_boxes takes (float32 cam, uint8 target, int32 gt_box[4], int64 iu[3])")
+    if not torch.is_tensor(gt_box) or not gt_box.is_cuda or gt_box.dtype != torch.int32 or gt_box.numel() != 4:
+        raise TypeError("eval_boxes: gt_box is an int32[4] device tensor (ops.eval_boxes_gt)")
+    H, W = cam.shape[-2:]
+    if tuple(target_u8.shape[-2:]) != (H, W) or cam.numel() != H * W:
+        raise ValueError(f"eval_boxes: cam {tuple(cam.shape)} and target {tuple(target_u8.shape)} differ")
+    nbytes = query("tris_eval_boxes_workspace_bytes", H, W)
+    if nbytes < 0:
+        raise ValueError(f"eval_boxes: {H}x{W} is beyond 2^24 pixels")
+    rows = 5 * (H * W + 1)
+    ws = workspace(nbytes + 256 + 4 * rows)
+    base = (ws.data_ptr() + 255) & ~255
+    record = torch.empty(EVAL_BOXES_RECORD, device=cam.device, dtype=torch.int32)
+    # the kept list is only handed out on request: otherwise it lives behind the workspace
+    boxes = torch.empty(H * W + 1, 5, device=cam.device, dtype=torch.int32) if return_boxes else None
+    call("tris_eval_boxes_f32", P(cam.contiguous()), P(target_u8.contiguous()), H, W, P(gt_box.contiguous()), P(iu), P(record),
+         boxes.data_ptr() if return_boxes else base + ((nbytes + 7) & ~7), base, _stream())
+    if not return_boxes:
+        return record
+    rec = decode_boxes_record(record.tolist())
+    if rec["n_prop"] == 0:
+        return record, [[0, 0, 1, 1, 0], [0, 0, 1, 1, 0]]
+    import numpy as np
+    out = []
+    for x, y, w, h, cnt in boxes[:rec["n_kept"]].tolist():
+        conf = float(np.float64(255 * cnt) / np.float64(w * h) / 255)       # numpy's uint8 slice .mean() / 255
+        out.append((float(x), float(y), float(x + w), float(y + h), conf))
+    return record, out
+
+
 # ------------------------------------------------------------------------------------- instance-mask synthesis (IRNet tail)
 # csrc/insseg.hip; the public functions with the reference's names are in tris_amd/irn.py
 def _chk_t(t, dtype):

@@ -7,8 +7,11 @@ Differences that do not change the returned numbers:
     recomputes them per sentence, validate.py:173-179);
   * resize / normalise / threshold / counting run in one device kernel chain (ops.eval_post) -- one host sync per
     sentence instead of several;
-  * the box metrics that the reference only prints (cv2 contours + torchvision NMS, validate.py:195-201) are not
-    produced (cv2 / torchvision are not part of this stack);
+  * HitM (the paper's PointM) and the box metrics the reference prints (validate.py:191-208: cv2 contours + torchvision NMS,
+    utils/box_eval_utils.py) are produced with TRIS_EVAL_BOXES=1 (cfg.eval_boxes, default off) by a device pass,
+    ops.eval_boxes (csrc/boxes.hip), that restates generate_bbox on the boolean mask without cv2 / torchvision; its records
+    ride the same host sync as the I/U counts.  The log lines then carry all six of the reference's metrics and
+    `last_metrics()` returns the three new ones.  The order of equal-confidence proposals is a project rule (DESIGN section 15);
   * under torch.distributed the five accumulators are all-reduced so every rank returns the global numbers
     (the reference returns rank-local meters).
 """
@@ -22,6 +25,20 @@ import torch
 from . import ops
 from .config import cfg
 from .utils.util import AverageMeter
+
+
+_LAST = None
+
+
+def last_metrics():
+    """HitM / box_mIOU / box_Acc of the last validate() call as {"hitm", "box_miou", "box_acc", "n_sent"} (percent, as the reference
+    prints them; after validate_same_sentence only "hitm" and "n_sent" are numbers), or None when cfg.eval_boxes was off."""
+    return None if _LAST is None else dict(_LAST)
+
+
+def _first_box(bbox):
+    """the one ground-truth box box_iou's diagonal reads (validate.py:200-201); zeros where a ref has none (its IoU is then 0)"""
+    return np.asarray(bbox[0], dtype=np.int64) if len(bbox) else np.zeros(4, np.int64)
 
 
 def _host(x):
@@ -64,6 +81,9 @@ def validate(args, data_loader, model, local_rank=0, visualize=False, logger=Non
     makes every row of every dense product independent of the rows it shares a launch with, so the returned (oIoU, mIoU, hit)
     are bit-for-bit those of the one-ref-at-a-time loop (TRIS_EVAL_GROUP=1: the reference's loop structure, trunk and sentence
     halves replayed from hipGraphs)."""
+    global _LAST
+    _LAST = None
+    boxes_on = bool(cfg.eval_boxes)
     num_steps = len(data_loader)
     model.eval()
     net = model.module if hasattr(model, "module") else model
@@ -75,6 +95,8 @@ def validate(args, data_loader, model, local_rank=0, visualize=False, logger=Non
         os.makedirs(args.cam_save_dir, exist_ok=True)
     batch_time, mIOU_meter = AverageMeter(), AverageMeter()
     st = {"I": 0, "U": 0, "n_sent": 0, "hit": 0}
+    # validate.py:148-149, 155, 207-208: hitmask_acc a Python int, box_mIOU_meter a float32 sum, box_Acc_meter an integer sum
+    bx = {"hitm": 0, "iou": np.float32(0), "acc": 0, "count": 0}
     cam_out_name = []
     graphs = {}
     group = max(1, int(cfg.eval_group))
@@ -84,8 +106,15 @@ def validate(args, data_loader, model, local_rank=0, visualize=False, logger=Non
     post = ops.eval_post_signed if signed else ops.eval_post
     end = time.time()
 
-    def account(idx, j, img_id, bbox, I, U, am, cam, n_img):
+    def account(idx, j, img_id, bbox, I, U, am, cam, n_img, rec=None):
         """one (image, sentence) result -> the meters, in the reference's order (validate.py:180-236)"""
+        if rec is not None:
+            r = ops.decode_boxes_record(rec)
+            bx["hitm"] += r["hitm"]
+            if len(bbox):
+                bx["iou"] = np.float32(bx["iou"] + r["box_miou"] * np.float32(n_img))
+                bx["acc"] += r["box_acc"] * n_img
+            bx["count"] += n_img
         st["n_sent"] += 1
         st["I"] += I
         st["U"] += U
@@ -101,8 +130,13 @@ def validate(args, data_loader, model, local_rank=0, visualize=False, logger=Non
             cam_out_name.append(f"{idx}_{j}_{img_id}")
 
     def report(idx):
+        more = ""
+        if boxes_on:
+            c = max(bx["count"], 1)
+            more = (f"HitM {bx['hitm'] / max(st['n_sent'], 1) * 100:.3f} | box_mIOU {100 * float(bx['iou']) / c:.3f} | "
+                    f"box_Acc {100 * bx['acc'] / c:.3f} | ")
         say(f"Test: [{idx:4d}/{num_steps}] | mIOU {100 * mIOU_meter.avg:.3f} | Overall IOU "
-            f"{100 * float(st['I']) / max(float(st['U']), 1.0):.3f} | Hit {st['hit'] / max(st['n_sent'], 1) * 100:.3f} | "
+            f"{100 * float(st['I']) / max(float(st['U']), 1.0):.3f} | Hit {st['hit'] / max(st['n_sent'], 1) * 100:.3f} | {more}"
             f"Time {batch_time.val:.3f} ({batch_time.avg:.3f})")
 
     def flush(refs):
@@ -115,19 +149,25 @@ def validate(args, data_loader, model, local_rank=0, visualize=False, logger=Non
         ids = torch.cat([r[3][0].t() for r in refs], 0).contiguous()                       # [sum S, L]
         owner = [i for i, r in enumerate(refs) for _ in range(r[3].size(-1))]
         maps = net.forward_pairs(vis, ids, owner, imgs.shape[2])                           # [sum S, 1, H, W]
-        ius, cams, k = [], [], 0
-        for r in refs:
+        ius, cams, recs, k = [], [], [], 0
+        gts = ops.eval_boxes_gt(np.stack([_first_box(r[5]) for r in refs])) if boxes_on else None
+        for i, r in enumerate(refs):
             for _ in range(r[3].size(-1)):
                 iu, cam = post(maps[k:k + 1], r[4])
                 ius.append(iu)
                 cams.append(cam)
+                if boxes_on:
+                    recs.append(ops.eval_boxes(cam, r[4], gts[i], iu))
                 k += 1
-        vals = torch.stack(ius).tolist()                                                   # the one host sync of the group
+        vals = torch.stack(ius)
+        if boxes_on:                                                                       # the records ride the same sync
+            vals = torch.cat([vals, torch.stack(recs).view(torch.int64)], 1)
+        vals = vals.tolist()                                                               # the one host sync of the group
         k = 0
         for idx, img_id, img, word_ids, tgt, bbox in refs:
             for j in range(word_ids.size(-1)):
-                I, U, am = vals[k]
-                account(idx, j, img_id, bbox, I, U, am, cams[k], img.size(0))
+                I, U, am = vals[k][:3]
+                account(idx, j, img_id, bbox, I, U, am, cams[k], img.size(0), vals[k][3:] if boxes_on else None)
                 k += 1
             batch_time.update((time.time() - end) / len(refs))
             if idx % args.print_freq == 0:
@@ -153,6 +193,7 @@ def validate(args, data_loader, model, local_rank=0, visualize=False, logger=Non
                     pending = []
                 continue
             gr = None if signed else _graphed(net, img, word_ids.shape[1], graphs)
+            gt = ops.eval_boxes_gt(_first_box(bbox))[0] if boxes_on else None
             if gr is not None:
                 gr.visual(img)                                                                 # once per image (hipGraph)
             else:
@@ -164,8 +205,11 @@ def validate(args, data_loader, model, local_rank=0, visualize=False, logger=Non
                 else:
                     out = gr.sentence(wid) if gr is not None else net.forward_cached(vis, wid, img.shape[2])  # [1,1,H,W]
                 iu, cam = post(out, tgt)
-                I, U, am = iu.tolist()                                                         # the one host sync
-                account(idx, j, img_id, bbox, I, U, am, cam, img.size(0))
+                if boxes_on:
+                    iu = torch.cat([iu, ops.eval_boxes(cam, tgt, gt, iu).view(torch.int64)])
+                vals = iu.tolist()                                                             # the one host sync
+                I, U, am = vals[:3]
+                account(idx, j, img_id, bbox, I, U, am, cam, img.size(0), vals[3:] if boxes_on else None)
             batch_time.update(time.time() - end)
             end = time.time()
             if idx % args.print_freq == 0:
@@ -184,7 +228,19 @@ def validate(args, data_loader, model, local_rank=0, visualize=False, logger=Non
     overall_IoU = 100 * I_t / max(U_t, 1.0)
     mIOU = torch.tensor(100 * iou_sum / max(iou_cnt, 1.0))
     hit = 100 * hits / max(nsent, 1.0)
-    say(f"Test: mIOU {float(mIOU):.5f}  Overall IOU {overall_IoU:.5f}  HiT {hit:.3f}")
+    more = ""
+    if boxes_on:
+        # validate.py:240-247: 100 * AverageMeter.avg of a float32 sum / of an integer sum (true division: float32)
+        hitm_t, iou_t, acc_t, cnt_t = float(bx["hitm"]), float(bx["iou"]), float(bx["acc"]), float(bx["count"])
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:   # the second reduce: only with the knob on
+            acc2 = torch.tensor([hitm_t, iou_t, acc_t, cnt_t], dtype=torch.float64, device="cuda")
+            dist.all_reduce(acc2)
+            hitm_t, iou_t, acc_t, cnt_t = acc2.tolist()
+        cnt32 = np.float32(max(cnt_t, 1.0))
+        _LAST = {"hitm": hitm_t / max(nsent, 1.0) * 100, "box_miou": float(np.float32(100) * (np.float32(iou_t) / cnt32)),
+                 "box_acc": float(np.float32(100) * (np.float32(acc_t) / cnt32)), "n_sent": int(nsent)}
+        more = f"  HitM {_LAST['hitm']:.3f}  box_mIOU {_LAST['box_miou']}  box_acc {_LAST['box_acc']}"
+    say(f"Test: mIOU {float(mIOU):.5f}  Overall IOU {overall_IoU:.5f}  HiT {hit:.3f}{more}")
     return overall_IoU, mIOU, hit
 
 
@@ -197,6 +253,10 @@ def validate_same_sentence(args, data_loader, model, local_rank=0, visualize=Fal
     does, :336-344).  Here the S foreground images go through the aux ViT as ONE batch and the S sentences through the
     text tower once (the reference runs S*S single forwards)."""
     from .CLIP import clip as _clip
+    global _LAST
+    _LAST = None
+    boxes_on = bool(cfg.eval_boxes)
+    hitm_acc = 0
     num_steps = len(data_loader)
     model.eval()
     net = model.module if hasattr(model, "module") else model
@@ -236,7 +296,12 @@ def validate_same_sentence(args, data_loader, model, local_rank=0, visualize=Fal
         score = ops.matmul(f_i, f_t, tB=True).sum(dim=1)                                   # [S]  (validate.py:327-329)
         best = int(torch.argmax(score).item())                                             # first maximum, as `>` does
         iu, cam = ops.eval_post(maps[best], tgt)
-        I, U, am = iu.tolist()
+        if boxes_on:                                                                       # HitM only (validate.py:346-348)
+            iu = torch.cat([iu, ops.eval_boxes(cam, tgt, ops.eval_boxes_gt(_first_box(bbox))[0], iu).view(torch.int64)])
+        vals = iu.tolist()
+        I, U, am = vals[:3]
+        if boxes_on:
+            hitm_acc += ops.decode_boxes_record(vals[3:])["hitm"] * S
         I_sum += float(I) * S * S
         U_sum += float(U) * S * S
         mIOU_meter.update(I / U if U > 0 else 0.0, img.size(0) * S)
@@ -253,12 +318,17 @@ def validate_same_sentence(args, data_loader, model, local_rank=0, visualize=Fal
             cam_out_name.append(f"{idx}_{img_id}")
         if idx % args.print_freq == 0:
             say(f"Test: [{idx:4d}/{num_steps}] | mIOU {100 * mIOU_meter.avg:.3f} | Overall IOU "
-                f"{100 * I_sum / max(U_sum, 1.0):.3f} | Hit {hit_acc / max(n_sent, 1) * 100:.3f}")
+                f"{100 * I_sum / max(U_sum, 1.0):.3f} | Hit {hit_acc / max(n_sent, 1) * 100:.3f}"
+                + (f" | HitM {hitm_acc / max(n_sent, 1) * 100:.3f}" if boxes_on else ""))
     if args.name_save_dir is not None and save_cam:
         with open(os.path.join(args.name_save_dir, f"{args.dataset}_train_names.json"), "w") as f:
             f.write(json.dumps(cam_out_name))
     overall_IoU = 100 * I_sum / max(U_sum, 1.0)
     mIOU = torch.tensor(100 * mIOU_meter.avg)
     hit = 100 * hit_acc / max(n_sent, 1)
-    say(f"Test: mIOU {float(mIOU):.5f}  Overall IOU {overall_IoU:.5f}  HiT {hit:.3f}")
+    more = ""
+    if boxes_on:
+        _LAST = {"hitm": hitm_acc / max(n_sent, 1) * 100, "box_miou": None, "box_acc": None, "n_sent": int(n_sent)}
+        more = f"  HitM {_LAST['hitm']:.3f}"
+    say(f"Test: mIOU {float(mIOU):.5f}  Overall IOU {overall_IoU:.5f}  HiT {hit:.3f}{more}")
     return overall_IoU, mIOU, hit
