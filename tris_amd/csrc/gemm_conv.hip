@@ -575,7 +575,7 @@ extern "C" int tris_conv3x3_fwd_f32(const float* X, const float* Wt, float* Y, i
   p.fastB = p.vecB;
   if (const int rows = run_stem_conv1(X, Wt, Y, B, H, W, Cin, Cout, stride, nullptr, (hipStream_t)stream))
     return rows > 0 ? 0 : (int)hipErrorLaunchFailure;
-  H2Guard h2(p, h2n);   // (armed: the implicit GEMM in h2 -- the direct kernels exist in x3 only)
+  H2Guard h2(p, h2n);   // (armed and served by the fast kernels: h2, implicit GEMM or direct kernel alike -- run_halo picks the unit)
   if (h2.bad) return (int)hipErrorInvalidValue;
   return conv3_dispatch<B_NK>(p, (hipStream_t)stream, nullptr);
 }
