@@ -131,7 +131,7 @@ def own_masks(pre):
 
 
 def masks_from_buffers(keep):
-    """the ReLU masks of a GPU forward, from the buffers ops.irn_heads leaves in `keep` (channels-last) -> {branch: bool [B,C,h,w]}"""
+    """the ReLU masks of a GPU forward, from the buffers IrnTrainer.heads leaves in `keep` (channels-last) -> {branch: bool [B,C,h,w]}"""
     cut = lambda t, a, b: (t[..., a:b] > 0).permute(0, 3, 1, 2).cpu()
     m = {f"fc_edge{i + 1}": cut(keep["cat_e"], 32 * i, 32 * i + 32) for i in range(5)}
     m.update(fc_dp1=cut(keep["cat7"], 0, 64), fc_dp2=cut(keep["cat7"], 64, 192), fc_dp6=cut(keep["cat7"], 192, 448),

@@ -406,3 +406,22 @@ def test_inference_is_unchanged_by_a_trainer(filled, arith):
     after = net.forward_raw(img)
     for k in ("edge_out", "dp_out", "edge", "dp"):
         assert torch.equal(before[k], after[k]), k
+
+
+def test_training_and_inference_run_the_same_heads(filled, arith):
+    """the taps of one uint8 forward (37 x 53: the x2 / x4 branches overhang the crop), passed through IrnTrainer.heads, give
+    the inference's own edge_out and dp_out bit for bit: with mean_shift.running_mean at zero the two modes are one computation
+    (irn_net.run_heads).  Measured before the two forwards were merged (commit db53847): equal in both arithmetics."""
+    from tris_amd.utils.synth import irn_image
+    net = _net(filled)
+    net.mean_shift.running_mean.zero_()
+    raw = net.forward_raw(irn_image(37, 53, seed=3), taps=True)
+    tr = _trainer(filled)
+    with tr.scope(), torch.no_grad():
+        edge_out, dp_out = tr.heads(raw["taps"])
+    pairs = (("edge_out", edge_out[:, 0], raw["edge_out"]), ("dp_out", dp_out.permute(0, 2, 3, 1), raw["dp_out"]))
+    for name, got, want in pairs:
+        assert got.shape == want.shape
+        print(f"[{arith}] {name}: largest |training - inference| {float((got - want).abs().max()):.3e}")
+    for name, got, want in pairs:
+        assert torch.equal(got, want), name

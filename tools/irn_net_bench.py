@@ -82,8 +82,8 @@ def main():
                 x1, taps = out["taps"][0], out["taps"]
                 r["stem_pool_ms"] = timed(lambda: net._stem(img), args.reps, args.inner)
                 r["trunk_ms"] = timed(lambda: net._trunk(x1), args.reps, args.inner)
-                r["edge_branch_ms"] = timed(lambda: net._edge_branch(taps), args.reps, args.inner)
-                r["dp_branch_ms"] = timed(lambda: net._dp_branch(taps), args.reps, args.inner)
+                r["edge_branch_ms"] = timed(lambda: net.heads(taps, only="edge"), args.reps, args.inner)
+                r["dp_branch_ms"] = timed(lambda: net.heads(taps, only="dp"), args.reps, args.inner)
             r["network_ms"] = timed(lambda: net(img), args.reps, args.inner)
 
             def end_to_end():

@@ -5,11 +5,12 @@
 //   confidence = foreground share of the rectangle, double, from an int32 summed-area table
 //   NMS        = torchvision's CPU loop on the (x, y, w, h) rows read as (x1, y1, x2, y2), float32, threshold 0.05
 // Both colours are labelled in ONE union-find over nodes 0..H*W: node 0 is the outside of the image, pixel p is node p + 1.  A
-// parent is always a smaller node than its child (the cc_find / cc_unite pattern of insseg.hip), so a root is its component's
+// parent is always a smaller node than its child (unionfind.h, shared with insseg.hip), so a root is its component's
 // first raster pixel -- the project's tie key -- and every background component that touches the frame has root 0.
 #include <limits.h>
 #include "common.h"
 #include "tris_hip.h"
+#include "unionfind.h"
 
 namespace {
 struct BoxWs {
@@ -46,34 +47,6 @@ inline long box_ws_layout(long n, BoxWs* w, char* base) {
   return o;
 }
 
-__device__ __forceinline__ int bx_load(const int* L, int a) { return __atomic_load_n(&L[a], __ATOMIC_RELAXED); }
-__device__ __forceinline__ int bx_find(int* L, int a) {
-  int p = bx_load(L, a);
-  while (p != a) {
-    int g = bx_load(L, p);
-    if (g != p) atomicMin(&L[a], g);   // path halving: only ever lowers a parent to one of its ancestors
-    a = p;
-    p = g;
-  }
-  return a;
-}
-__device__ __forceinline__ void bx_unite(int* L, int a, int b) {
-  while (true) {
-    a = bx_find(L, a);
-    b = bx_find(L, b);
-    if (a == b) return;
-    if (a < b) { int t = a; a = b; b = t; }
-    int old = atomicMin(&L[a], b);
-    if (old == a) return;
-    a = old;                          // a was no root any more: unite its new parent with b
-  }
-}
-__device__ __forceinline__ int bx_root(const int* L, int a) {   // read-only walk (after the merge pass)
-  int q = bx_load(L, a);
-  while (q != a) { a = q; q = bx_load(L, a); }
-  return a;
-}
-
 // mask = cam > 1e-9; every pixel starts linked to its upper neighbour of the same colour, else to its left one, else to itself;
 // a background pixel of the first row / column starts linked to the outside node
 __global__ __launch_bounds__(256) void bx_init_kernel(const float* __restrict__ cam, int H, int W, BoxWs w) {
@@ -92,15 +65,13 @@ __global__ __launch_bounds__(256) void bx_init_kernel(const float* __restrict__ 
   w.minx[node] = INT_MAX; w.miny[node] = INT_MAX; w.maxx[node] = -1; w.maxy[node] = -1;
   if (p == 0) { w.parent[0] = 0; w.minx[0] = INT_MAX; w.miny[0] = INT_MAX; w.maxx[0] = -1; w.maxy[0] = -1; }
 }
-// parent[i] <- the root of i.  Concurrent writers only ever store an ancestor, so a reader always sees a valid (if longer) chain.
+// parent[i] <- the root of i
 __global__ __launch_bounds__(256) void bx_compress_kernel(int* parent, int N) {
   int i = blockIdx.x * 256 + threadIdx.x + 1;
   if (i >= N) return;
-  int a = bx_load(parent, i);
+  int a = uf_load(parent, i);
   if (a == i) return;
-  int q = bx_load(parent, a);
-  while (q != a) { a = q; q = bx_load(parent, a); }
-  __atomic_store_n(&parent[i], a, __ATOMIC_RELAXED);
+  __atomic_store_n(&parent[i], uf_root(parent, a), __ATOMIC_RELAXED);
 }
 // the adjacencies the initial links do not cover: foreground 8-connected, background 4-connected + the frame
 __global__ __launch_bounds__(256) void bx_merge_kernel(int H, int W, BoxWs w) {
@@ -112,15 +83,15 @@ __global__ __launch_bounds__(256) void bx_merge_kernel(int H, int W, BoxWs w) {
   unsigned char c = m[p];
   bool U = y > 0 && m[p - W] == c, L = x > 0 && m[p - 1] == c;
   if (c) {
-    if (U && L) bx_unite(w.parent, node, node - 1);
+    if (U && L) uf_unite(w.parent, node, node - 1);
     if (!U && y > 0) {   // (with an upper neighbour both diagonals are 4-adjacent to it)
-      if (x > 0 && !L && m[p - W - 1]) bx_unite(w.parent, node, node - W - 1);
-      if (x < W - 1 && m[p - W + 1]) bx_unite(w.parent, node, node - W + 1);
+      if (x > 0 && !L && m[p - W - 1]) uf_unite(w.parent, node, node - W - 1);
+      if (x < W - 1 && m[p - W + 1]) uf_unite(w.parent, node, node - W + 1);
     }
   } else {
     if (y == 0 || x == 0) return;
-    if (U && L) bx_unite(w.parent, node, node - 1);
-    if (y == H - 1 || x == W - 1) bx_unite(w.parent, node, 0);
+    if (U && L) uf_unite(w.parent, node, node - 1);
+    if (y == H - 1 || x == W - 1) uf_unite(w.parent, node, 0);
   }
 }
 // inclusive row sums of the mask: one block per row
@@ -176,9 +147,9 @@ __global__ __launch_bounds__(256) void bx_rect_kernel(int H, int W, BoxWs w) {
     unsigned char c = m[p];
     bool bl = x == 0 || m[p - 1] != c, br = x == W - 1 || m[p + 1] != c;
     bool bu = y == 0 || m[p - W] != c, bd = y == H - 1 || m[p + W] != c;
-    isroot = bx_load(w.parent, i) == i;
+    isroot = uf_load(w.parent, i) == i;
     if (bl || br || bu || bd) {
-      int r = bx_root(w.parent, i);
+      int r = uf_root(w.parent, i);
       if (r != 0) {
         if (bl) atomicMin(&w.minx[r], x);
         if (br) atomicMax(&w.maxx[r], x);
@@ -191,14 +162,6 @@ __global__ __launch_bounds__(256) void bx_rect_kernel(int H, int W, BoxWs w) {
   int cnt = __syncthreads_count(isroot);
   if (threadIdx.x == 0) w.tcount[blockIdx.x] = cnt;
 }
-__device__ __forceinline__ int block_isum_256(int v, int* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 __device__ __forceinline__ int bx_sat(const int* sat, int W, int y, int x) { return (y < 0 || x < 0) ? 0 : sat[(long)y * W + x]; }
 // roots -> proposals in raster order, with their counts and confidences
 __global__ __launch_bounds__(256) void bx_emit_kernel(int H, int W, BoxWs w) {
@@ -209,7 +172,7 @@ __global__ __launch_bounds__(256) void bx_emit_kernel(int H, int W, BoxWs w) {
   const int off = block_isum_256(part, red);
   if (w.tcount[blockIdx.x] == 0) return;   // (uniform: also every tile of a degenerate mask)
   int i = blockIdx.x * 256 + threadIdx.x;
-  bool isroot = i >= 1 && i < N && bx_load(w.parent, i) == i;
+  bool isroot = i >= 1 && i < N && uf_load(w.parent, i) == i;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned long long b = __ballot(isroot);
   if (lane == 0) wcnt[wave] = __popcll(b);
@@ -256,8 +219,7 @@ __global__ __launch_bounds__(256) void bx_nms_kernel(const unsigned char* __rest
   const int P = block_isum_256(part, red);
   double dm = 0.0;
   for (int j = threadIdx.x; j < P; j += 256) dm = fmax(dm, w.conf[j]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) dm = fmax(dm, __shfl_xor(dm, o, 64));
+  dm = wave_max_f64(dm);
   if (lane == 0) dred[wave] = dm;
   __syncthreads();
   const double cmax = fmax(fmax(dred[0], dred[1]), fmax(dred[2], dred[3]));

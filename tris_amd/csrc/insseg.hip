@@ -8,6 +8,7 @@
 #include "common.h"
 #include "tris_hip.h"
 #include "bilinear.h"
+#include "unionfind.h"
 
 namespace {
 
@@ -56,30 +57,8 @@ __global__ __launch_bounds__(256) void irn_weak_mask_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------- connected-component labelling
-// Union-find on the pixel grid (4-connectivity), in the manner of Komura's label-equivalence method.  A parent is always a smaller linear index than its child, so a component's
+// Union-find on the pixel grid (4-connectivity, unionfind.h), in the manner of Komura's label-equivalence method.  A component's
 // root is its minimum linear index = its first pixel in raster order; ranking the roots by index gives skimage's numbering.
-__device__ __forceinline__ int cc_load(const int* L, int a) { return __atomic_load_n(&L[a], __ATOMIC_RELAXED); }
-__device__ __forceinline__ int cc_find(int* L, int a) {
-  int p = cc_load(L, a);
-  while (p != a) {
-    int g = cc_load(L, p);
-    if (g != p) atomicMin(&L[a], g);   // path halving: only ever lowers a parent to one of its ancestors
-    a = p;
-    p = g;
-  }
-  return a;
-}
-__device__ __forceinline__ void cc_unite(int* L, int a, int b) {
-  while (true) {
-    a = cc_find(L, a);
-    b = cc_find(L, b);
-    if (a == b) return;
-    if (a < b) { int t = a; a = b; b = t; }
-    int old = atomicMin(&L[a], b);
-    if (old == a) return;
-    a = old;                          // a was no root any more: unite its new parent with b
-  }
-}
 // Every foreground pixel starts linked to its upper neighbour, else to its left one, else to itself: the links already span each
 // component except where a pixel has both neighbours, and only those pairs are united (with atomics) after a compression pass
 // has shortened the chains -- in a solid region they then meet at a common root at once and no atomic is issued.
@@ -93,16 +72,14 @@ __global__ __launch_bounds__(256) void cc_init_kernel(const unsigned char* __res
   if (im[p]) v = (p >= W && im[p - W]) ? p - W : ((p % W) > 0 && im[p - 1]) ? p - 1 : p;
   parent[o + p] = v;
 }
-// parent[p] <- the root of p.  Concurrent writers only ever store an ancestor, so a reader always sees a valid (if longer) chain.
+// parent[p] <- the root of p
 __global__ __launch_bounds__(256) void cc_compress_kernel(int* parent, int n) {
   int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   int* L = parent + (long)blockIdx.y * n;
-  int a = cc_load(L, p);
+  int a = uf_load(L, p);
   if (a < 0 || a == p) return;
-  int q = cc_load(L, a);
-  while (q != a) { a = q; q = cc_load(L, a); }
-  __atomic_store_n(&L[p], a, __ATOMIC_RELAXED);
+  __atomic_store_n(&L[p], uf_root(L, a), __ATOMIC_RELAXED);
 }
 __global__ __launch_bounds__(256) void cc_merge_kernel(const unsigned char* __restrict__ img, int H, int W, int* parent) {
   int n = H * W;
@@ -111,7 +88,7 @@ __global__ __launch_bounds__(256) void cc_merge_kernel(const unsigned char* __re
   long o = (long)blockIdx.y * n;
   const unsigned char* im = img + o;
   if (!im[p]) return;
-  if (p >= W && im[p - W] && (p % W) > 0 && im[p - 1]) cc_unite(parent + o, p, p - 1);   // (the other links are the initial ones)
+  if (p >= W && im[p - W] && (p % W) > 0 && im[p - 1]) uf_unite(parent + o, p, p - 1);   // (the other links are the initial ones)
 }
 // root[p] = the root of p (or -1), flag[p] = p is a root
 __global__ __launch_bounds__(256) void cc_flatten_kernel(int* __restrict__ parent, int n, int* __restrict__ root,
@@ -119,12 +96,7 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(int* __restrict__ paren
   int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   long o = (long)blockIdx.y * n;
-  int r = -1;
-  if (cc_load(parent + o, p) >= 0) {
-    r = p;
-    int q = cc_load(parent + o, r);
-    while (q != r) { r = q; q = cc_load(parent + o, r); }
-  }
+  int r = uf_load(parent + o, p) >= 0 ? uf_root(parent + o, p) : -1;
   root[o + p] = r;
   flag[o + p] = (r == p) ? 1 : 0;
 }

@@ -30,17 +30,6 @@ __device__ __forceinline__ int pair_class(int a, int b) {
 }
 __device__ __forceinline__ int sgn(double t) { return (t > 0.0) - (t < 0.0); }   // torch's sign: sign(0) = 0
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 inline size_t fwd_lds_bytes(int r) {
   const size_t tn = (size_t)(TS + r) * (TS + 2 * r);
   return tn * (sizeof(double) + 2 * sizeof(float) + 3 * sizeof(int) + 1);

@@ -182,11 +182,8 @@ __global__ __launch_bounds__(64) void gn_finalize_kernel(const double* __restric
     s += p[0];
     ss += p[1];
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s += __shfl_xor(s, o, 64);
-    ss += __shfl_xor(ss, o, 64);
-  }
+  s = wave_sum_f64(s);
+  ss = wave_sum_f64(ss);
   if (threadIdx.x != 0) return;
   const double mean = s / count;
   double var = ss / count - mean * mean;

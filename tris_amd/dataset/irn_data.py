@@ -36,8 +36,6 @@ import numpy as np
 from . import pil_tables
 from .._lib import CONSTS
 
-MEAN = (0.485, 0.456, 0.406)         # TorchvisionNormalize's defaults (dataloader.py:68)
-STD = (0.229, 0.224, 0.225)
 TILE, PATCH, KMAX, ND = (CONSTS[k] for k in ("TRIS_IRN_AUG_TILE", "TRIS_IRN_AUG_PATCH", "TRIS_IRN_AUG_KMAX", "TRIS_IRN_AUG_DESC"))
 # descriptor fields (csrc/irndata.hip)
 (D_IMG, D_LAB, D_H, D_W, D_HT, D_WT, D_CT, D_CB, D_CL, D_CR, D_IT, D_IB, D_IL, D_IR, D_FLAGS, D_KH, D_KV, D_COLB, D_COLK, D_ROWB,
@@ -46,9 +44,9 @@ ARENA_SLACK = 16                     # spare bytes behind the last image: the ke
 
 
 def normalisation_table():
-    """float32 [3, 256]: (v / 255. - mean) / std in double as the reference computes it on a uint8 array, stored as float32"""
-    v = np.arange(256, dtype=np.uint8)
-    return np.stack([((v / 255. - MEAN[c]) / STD[c]).astype(np.float32) for c in range(3)])
+    """float32 [3, 256] as numpy: the IRNet pipeline's one table, irn_net.normalize_table (MEAN and STD live beside it)"""
+    from ..irn_net import normalize_table
+    return normalize_table().numpy()
 
 
 # ------------------------------------------------------------------------------------------------------------------ the draw

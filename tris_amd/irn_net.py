@@ -8,14 +8,19 @@ The module is a holder of parameters and buffers under the reference's names (IR
 the computation is HIP kernels on channels-last activations: the ResNet-50 trunk's 1x1 and 3x3 products on the MFMA paths
 (ops.linear, ops.conv3x3), frozen BatchNorm as tris_bn_apply_f32 with an invstd formed once at load time, and the stem, pooling,
 GroupNorm / upsample / concatenation, narrow heads and flip-average of csrc/irnnet.hip.  Both flip rows go through the network as
-one B = 2 batch.  There is no CPU path: without a GPU forward raises ops.NoGpuError.  Training the two branches is
-tris_amd.irn_train; the CRF labels it trains on are not on this stack.
+one B = 2 batch.  There is no CPU path: without a GPU forward raises ops.NoGpuError.
+
+The wiring of fc_edge1..6 and fc_dp1..7 is stated once, in the tables EDGE / DP / BUFFERS below: the module construction, the
+forward of both branches (run_heads, which inference and training share) and the trainable-parameter order
+(head_parameter_names) are read off them.  Training the two branches is tris_amd.irn_train, whose
+backward walks the same tables; the CRF labels it trains on are tris_amd.crf.
 
 In the h2 arithmetic the products read fp32 activations and split them in their own loops (operand planes are a training-step
 construct: they are not used here).  The products take the cost model's tile choice (ops.autotune_off): image sizes change from
 call to call, and nothing may be cached per shape.
 """
 import re
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -29,9 +34,28 @@ LAYERS = (3, 4, 6, 3)
 STRIDES = (1, 2, 2, 1)           # of layer1..4: resnet50(strides=[2, 2, 2, 1]); strides[0] is the stem's
 BN_EPS = 1e-5
 GN_EPS = 1e-5
-# (input channels, output channels, GroupNorm groups, upsample factor) of fc_edge1..5 and fc_dp1..6
-EDGE = ((64, 32, 4, 1), (256, 32, 4, 1), (512, 32, 4, 2), (1024, 32, 4, 4), (2048, 32, 4, 4))
-DP = ((64, 64, 8, 1), (256, 128, 16, 1), (512, 256, 16, 1), (1024, 256, 16, 2), (2048, 256, 16, 2), (768, 256, 16, 2))
+# One GroupNorm branch (IRNet/net/resnet50_irn.py:29-86): relu(upsample(groupnorm(conv1x1(src)), x scale)), cropped, written into
+# channels [off, off + cout) of the buffer dst.  src: a tap index (x1..x5 are 0..4) or the buffer a branch before it filled.
+Branch = namedtuple("Branch", "name src cin cout groups scale dst off")
+# The narrow 1x1 convolution that closes a group of branches: it reads the buffer src
+Head = namedtuple("Head", "name src cin cout bias")
+EDGE = (Branch("fc_edge1", 0, 64, 32, 4, 1, "cat_e", 0),
+        Branch("fc_edge2", 1, 256, 32, 4, 1, "cat_e", 32),
+        Branch("fc_edge3", 2, 512, 32, 4, 2, "cat_e", 64),
+        Branch("fc_edge4", 3, 1024, 32, 4, 4, "cat_e", 96),
+        Branch("fc_edge5", 4, 2048, 32, 4, 4, "cat_e", 128))
+EDGE_HEAD = Head("fc_edge6", "cat_e", 160, 1, True)
+DP = (Branch("fc_dp1", 0, 64, 64, 8, 1, "cat7", 0),
+      Branch("fc_dp2", 1, 256, 128, 16, 1, "cat7", 64),
+      Branch("fc_dp3", 2, 512, 256, 16, 1, "cat6", 0),
+      Branch("fc_dp4", 3, 1024, 256, 16, 2, "cat6", 256),
+      Branch("fc_dp5", 4, 2048, 256, 16, 2, "cat6", 512),
+      Branch("fc_dp6", "cat6", 768, 256, 16, 2, "cat7", 192),
+      Branch("fc_dp7", "cat7", 448, 256, 16, 1, "a7", 0))
+DP_HEAD = Head("fc_dp7.3", "a7", 256, 2, False)
+GROUPS = {"edge": (EDGE, EDGE_HEAD), "dp": (DP, DP_HEAD)}
+# buffer -> (channels, the tap whose height and width it has)
+BUFFERS = {"cat_e": (160, 1), "cat6": (768, 2), "cat7": (448, 1), "a7": (256, 1)}
 
 
 # buffers of AffinityDisplacementLoss (IRNet/net/resnet50_irn.py:161-166) that a checkpoint saved by train_irn.py carries
@@ -42,6 +66,44 @@ def normalize_table():
     """float32 [3,256]: (v / 255 - mean) / std in float64, rounded once -- what TorchvisionNormalize stores for a uint8 v"""
     v = np.arange(256, dtype=np.float64)
     return torch.from_numpy(np.stack([((v / 255. - m) / s).astype(np.float32) for m, s in zip(MEAN, STD)]))
+
+
+def branch_names(b):
+    """the parameters of a Branch: its convolution weight, GroupNorm scale and GroupNorm bias"""
+    return f"{b.name}.0.weight", f"{b.name}.1.weight", f"{b.name}.1.bias"
+
+
+def head_parameter_names():
+    """(edge names, dp names): the reference's trainable_parameters() (resnet50_irn.py:141-143), canonical names in its order"""
+    return tuple([n for b in branches for n in branch_names(b)] + [f"{head.name}.weight"] + [f"{head.name}.bias"] * head.bias
+                 for branches, head in GROUPS.values())
+
+
+def run_heads(taps, prm, dp_bias=None, record=None, only=None):
+    """Net.forward's two branches (IRNet/net/resnet50_irn.py:123-139) on the taps x1..x5 (channels-last): -> {"edge": [B,h,w,1],
+    "dp": [B,h,w,2]}.  prm: canonical name -> tensor for every name of head_parameter_names().  dp_bias: what fc_dp7[3] adds --
+    inference passes -mean_shift.running_mean, training nothing (MeanShift is the identity in train mode, :111-114).  record: a
+    dict that receives the buffers of BUFFERS and, under "gn", {branch name: (GroupNorm input, statistics)}: what a backward
+    needs.  only: "edge" | "dp" runs that group alone."""
+    B, dev = taps[0].shape[0], taps[0].device
+    bufs, gn, out = {}, {}, {}
+    for key in GROUPS if only is None else (only,):
+        branches, head = GROUPS[key]
+        for b in branches:
+            if b.dst not in bufs:
+                C, tap = BUFFERS[b.dst]
+                bufs[b.dst] = torch.empty(B, *taps[tap].shape[1:3], C, dtype=torch.float32, device=dev)
+            dst = bufs[b.dst]
+            conv, gamma, beta = (prm[n] for n in branch_names(b))
+            t = ops.linear(taps[b.src] if isinstance(b.src, int) else bufs[b.src], conv)
+            st = ops.group_norm_stats(t, b.groups, GN_EPS)
+            gn[b.name] = (t, st)
+            ops.gn_apply_up(t, st, gamma, beta, b.groups, b.scale, dst.shape[1:3], True, dst, b.off)
+        bias = prm[f"{head.name}.bias"] if head.bias else dp_bias
+        out[key] = ops.irn_head(bufs[head.src], prm[f"{head.name}.weight"].reshape(head.cout, head.cin), bias)
+    if record is not None:
+        record.update(bufs, gn=gn)
+    return out
 
 
 def feat_size(H, W):
@@ -107,10 +169,6 @@ class _MeanShift(nn.Module):
         self.register_buffer("running_mean", torch.zeros(2))
 
 
-def _branch(cin, cout, groups):
-    return nn.Sequential(nn.Conv2d(cin, cout, 1, bias=False), nn.GroupNorm(groups, cout))
-
-
 class EdgeDisplacement(nn.Module):
     """Parameters and buffers under the reference's canonical names: resnet50.*, fc_edge1..6.*, fc_dp1..7.*,
     mean_shift.running_mean.  forward(img_u8 [H,W,3]) -> (edge [h,w], dp [2,h,w]) float32 on the device."""
@@ -119,13 +177,14 @@ class EdgeDisplacement(nn.Module):
         super().__init__()
         self.resnet50 = _Trunk()
         self.mean_shift = _MeanShift()
-        for i, (cin, cout, g, _) in enumerate(EDGE):
-            setattr(self, f"fc_edge{i + 1}", _branch(cin, cout, g))
-        self.fc_edge6 = nn.Conv2d(160, 1, 1, bias=True)
-        for i, (cin, cout, g, _) in enumerate(DP):
-            setattr(self, f"fc_dp{i + 1}", _branch(cin, cout, g))
-        self.fc_dp7 = nn.Sequential(nn.Conv2d(448, 256, 1, bias=False), nn.GroupNorm(16, 256), nn.Identity(),
-                                    nn.Conv2d(256, 2, 1, bias=False))
+        for branches, head in GROUPS.values():
+            for b in branches:
+                setattr(self, b.name, nn.Sequential(nn.Conv2d(b.cin, b.cout, 1, bias=False), nn.GroupNorm(b.groups, b.cout)))
+            conv = nn.Conv2d(head.cin, head.cout, 1, bias=head.bias)
+            if head is EDGE_HEAD:
+                self.fc_edge6 = conv
+            else:
+                self.fc_dp7.extend([nn.Identity(), conv])     # fc_dp7[3], behind the place of the reference's ReLU
         for p in self.parameters():
             p.requires_grad_(False)
         self.eval()
@@ -171,7 +230,7 @@ class EdgeDisplacement(nn.Module):
 
     def _prepare(self, dev):
         """derived constants, formed once per load: 1/sqrt(running_var + eps) of every frozen BatchNorm (float64, rounded once),
-        the stem weight as [7,7,3,64], 3x3 weights in the kernel layout, the heads' matrices, the normalisation table"""
+        the stem weight as [7,7,3,64], 3x3 weights in the kernel layout, the heads' parameters by name, the normalisation table"""
         if any(t.device != dev for t in self.state_dict(keep_vars=True).values()):
             raise ops.NoGpuError("EdgeDisplacement: move the module to the GPU first (.cuda()); there is no CPU fallback")
         ver = self._versions()
@@ -187,9 +246,7 @@ class EdgeDisplacement(nn.Module):
         self._prep = {
             "ver": self._versions(), "inv": inv, "lut": normalize_table().to(dev),
             "stem_w": r.conv1.weight.detach().permute(2, 3, 1, 0).contiguous(),
-            "edge_w": self.fc_edge6.weight.detach().reshape(1, 160).contiguous(),
-            "edge_b": self.fc_edge6.bias.detach().contiguous(),
-            "dp_w": self.fc_dp7[3].weight.detach().reshape(2, 256).contiguous(),
+            "heads": {n: self.get_parameter(n) for names in head_parameter_names() for n in names},
             "dp_b": (-self.mean_shift.running_mean.detach()).contiguous(),
         }
         return self._prep
@@ -221,31 +278,9 @@ class EdgeDisplacement(nn.Module):
             taps.append(x)
         return taps
 
-    def _gn_into(self, seq, x, groups, scale, size, out, c_off, relu=True):
-        t = ops.linear(x, seq[0].weight)
-        st = ops.group_norm_stats(t, groups, GN_EPS)
-        return ops.gn_apply_up(t, st, seq[1].weight, seq[1].bias, groups, scale, size, relu, out, c_off)
-
-    def _edge_branch(self, taps):
-        B, h, w, _ = taps[1].shape
-        cat = torch.empty(B, h, w, 160, dtype=torch.float32, device=taps[0].device)
-        for i, (_, cout, g, scale) in enumerate(EDGE):
-            self._gn_into(getattr(self, f"fc_edge{i + 1}"), taps[i], g, scale, (h, w), cat, cout * i)
-        return ops.irn_head(cat, self._prep["edge_w"], self._prep["edge_b"])[..., 0]
-
-    def _dp_branch(self, taps):
-        dev = taps[0].device
-        B, h, w, _ = taps[1].shape
-        _, h3, w3, _ = taps[2].shape
-        cat6 = torch.empty(B, h3, w3, 768, dtype=torch.float32, device=dev)
-        for j, i in enumerate((2, 3, 4)):
-            self._gn_into(getattr(self, f"fc_dp{i + 1}"), taps[i], DP[i][2], DP[i][3], (h3, w3), cat6, 256 * j)
-        cat7 = torch.empty(B, h, w, 448, dtype=torch.float32, device=dev)
-        self._gn_into(self.fc_dp1, taps[0], DP[0][2], 1, (h, w), cat7, 0)
-        self._gn_into(self.fc_dp2, taps[1], DP[1][2], 1, (h, w), cat7, 64)
-        self._gn_into(self.fc_dp6, cat6, DP[5][2], DP[5][3], (h, w), cat7, 192)
-        a7 = self._gn_into(self.fc_dp7, cat7, 16, 1, (h, w), None, 0)
-        return ops.irn_head(a7, self._prep["dp_w"], self._prep["dp_b"])
+    def heads(self, taps, only=None):
+        """run_heads in eval mode: the mean shift is subtracted in fc_dp7[3]'s bias"""
+        return run_heads(taps, self._prep["heads"], self._prep["dp_b"], only=only)
 
     # ------------------------------------------------------------------------------------------------------------ forward
     def _image(self, img):
@@ -274,8 +309,8 @@ class EdgeDisplacement(nn.Module):
             if ops.h2_on() and not ops._H2.get("in_step") and not ops._H2.get("private"):
                 ops.h2_begin_step(explicit=False)     # a fresh amax pool: the pass never straddles two
             t = self._trunk(self._stem(img))
-            edge_out = self._edge_branch(t)
-            dp_out = self._dp_branch(t)
+            y = self.heads(t)
+            edge_out, dp_out = y["edge"][..., 0], y["dp"]
             edge, dp = ops.irn_net_finish(edge_out, dp_out)
         out = {"edge_out": edge_out, "dp_out": dp_out, "edge": edge, "dp": dp}
         if taps:

@@ -10,7 +10,9 @@ its closing mean-shift pass (:93-106) on this stack.
 
 The reference detaches every trunk tap (IRNet/net/resnet50_irn.py:117-121) and keeps the backbone in eval mode (:145-147): the
 ResNet-50 runs forward only, under no_grad, on the inference kernels of tris_amd.irn_net behind a float stem; fc_edge1..6 and
-fc_dp1..7 train (ops.IrnHeadsFn, csrc/irntrain.hip), the loss is tris_amd.irn_loss, the optimiser tris_amd.optim.PolySGD.
+fc_dp1..7 train (IrnHeadsFn below, csrc/irntrain.hip), the loss is tris_amd.irn_loss, the optimiser tris_amd.optim.PolySGD.
+IrnHeadsFn lives here and not in irn_net because only training needs a backward: its forward is irn_net.run_heads, the one
+inference runs, and its backward walks irn_net's branch tables.
 Train-mode semantics: MeanShift is the identity (:111-114), there is no flip-average.  There is no CPU path: ops.NoGpuError.
 The dataset, its augmentation and the command line: tris_amd.dataset.irn_data, tris_amd.train_irn.
 Not here: the CRF labels, data parallelism, graph capture of the step.
@@ -20,17 +22,96 @@ import contextlib
 import torch
 
 from . import irn_loss, ops
-from .irn_net import EDGE, DP, EdgeDisplacement
+from .irn_net import GROUPS, EdgeDisplacement, branch_names, head_parameter_names, run_heads
 from .optim import PolySGD
 
+N_TAPS = 5
+HEAD_NAMES = tuple(n for names in head_parameter_names() for n in names)      # the order IrnHeadsFn takes the parameters in
 
-def head_parameter_names():
-    """(edge names, dp names): the reference's trainable_parameters() (resnet50_irn.py:141-143), canonical names in its order"""
-    edge = [f"fc_edge{i + 1}.{s}" for i in range(len(EDGE)) for s in ("0.weight", "1.weight", "1.bias")]
-    edge += ["fc_edge6.weight", "fc_edge6.bias"]
-    dp = [f"fc_dp{i + 1}.{s}" for i in range(len(DP)) for s in ("0.weight", "1.weight", "1.bias")]
-    dp += ["fc_dp7.0.weight", "fc_dp7.1.weight", "fc_dp7.1.bias", "fc_dp7.3.weight"]
-    return edge, dp
+
+def _wgrad_1x1(p, dt, x, needs):
+    """dW [N,K] = dt^T x for a 1x1 convolution weight, on the dense-product path; into the parameter's arena view if it has one"""
+    N, K = dt.shape[-1], x.shape[-1]
+    M = x.numel() // K
+    return ops._emit(p, lambda o: ops.gemm(dt, x, o, N, K, M, N, K, K, True, False, mark=False), needs)
+
+
+def _dgrad_1x1(dt, w):
+    """dX [M,K] = dt w for a 1x1 convolution weight [N,K,1,1]"""
+    N = dt.shape[-1]
+    K = w.numel() // N
+    M = dt.numel() // N
+    dx = torch.empty(*dt.shape[:-1], K, dtype=torch.float32, device=dt.device)
+    ops.gemm(dt, w, dx, M, K, N, N, K, K, False, False, w_b=True, w_bt=True)
+    return dx
+
+
+def _backward_order(branches, head):
+    """the branches in an order that has every buffer's gradient complete before a branch that wrote into it runs: buffer by
+    buffer from the head's, each buffer's writers in table order, a buffer that a branch reads queued behind"""
+    queue = [head.src]
+    for buf in queue:
+        for b in branches:
+            if b.dst == buf:
+                yield b
+                if not isinstance(b.src, int):
+                    queue.append(b.src)
+
+
+class IrnHeadsFn(torch.autograd.Function):
+    """Net.forward's two branches in train mode (irn_net.run_heads without a dp bias): taps x1..x5 (channels-last, detached) and
+    the head parameters in HEAD_NAMES order -> edge_out [B,1,h,w], dp_out [B,2,h,w].  The Function owns the concatenation buffers,
+    the GroupNorm inputs and their statistics, and runs the backward in one fixed order; the only data gradients formed are those
+    of the branches that read a buffer (fc_dp7's and fc_dp6's inputs; no tap has one)."""
+
+    @staticmethod
+    def forward(ctx, keep, *args):
+        taps, prm = args[:N_TAPS], args[N_TAPS:]
+        if len(prm) != len(HEAD_NAMES):
+            raise ValueError(f"IrnHeadsFn takes {len(HEAD_NAMES)} parameters, got {len(prm)}")
+        ops._chk(*taps, *prm)
+        ctx.taps, ctx.prm, ctx.rec = [t.contiguous() for t in taps], dict(zip(HEAD_NAMES, prm)), {}
+        y = run_heads(ctx.taps, ctx.prm, record=ctx.rec)
+        if keep is not None:
+            keep.update({k: v for k, v in ctx.rec.items() if k != "gn"})
+        return tuple(y[k].permute(0, 3, 1, 2).contiguous() for k in GROUPS)      # (no copy of the one-channel edge map)
+
+    @staticmethod
+    def backward(ctx, *g_out):
+        taps, prm, rec = ctx.taps, ctx.prm, ctx.rec
+        need = dict(zip(HEAD_NAMES, ctx.needs_input_grad[1 + N_TAPS:]))
+        if any(ctx.needs_input_grad[1:1 + N_TAPS]):
+            raise RuntimeError("irn_heads: the taps are detached in the reference (resnet50_irn.py:117-121); they take no gradient")
+        out = dict.fromkeys(HEAD_NAMES)
+
+        def emit(name, value, sink):
+            """a gradient the kernel wrote: None to autograd when it went into the parameter's arena view or is not asked for"""
+            out[name] = value.view_as(prm[name]) if sink is None and need[name] else None
+
+        for (branches, head), g in zip(GROUPS.values(), g_out):
+            x = rec[head.src]
+            if g is None:
+                g = torch.zeros(x.shape[0], head.cout, *x.shape[1:3], dtype=torch.float32, device=x.device)
+            wn, bn = f"{head.name}.weight", f"{head.name}.bias"
+            sw, sb = ops._sink(prm[wn]), ops._sink(prm[bn]) if head.bias else None
+            d_x, dw, db = ops.irn_head_bwd(g.permute(0, 2, 3, 1).contiguous(), x, prm[wn].reshape(head.cout, head.cin),
+                                           want_db=head.bias, dw=sw, db=sb)
+            emit(wn, dw, sw)
+            if head.bias:
+                emit(bn, db, sb)
+            d = {head.src: d_x}                    # buffer -> its gradient
+            for b in _backward_order(branches, head):
+                conv, gamma, beta = branch_names(b)
+                t, st = rec["gn"][b.name]
+                sg, sb = ops._sink(prm[gamma]), ops._sink(prm[beta])
+                dt, dgam, dbet = ops.gn_up_bwd(d[b.dst], rec[b.dst], b.off, t, st, prm[gamma], b.groups, b.scale,
+                                               dgamma=sg, dbeta=sb)
+                out[conv] = _wgrad_1x1(prm[conv], dt, taps[b.src] if isinstance(b.src, int) else rec[b.src], need[conv])
+                emit(gamma, dgam, sg)
+                emit(beta, dbet, sb)
+                if not isinstance(b.src, int):
+                    d[b.src] = _dgrad_1x1(dt, prm[conv])
+        return (None,) * (1 + N_TAPS) + tuple(out[n] for n in HEAD_NAMES)
 
 
 class IrnTrainer:
@@ -83,8 +164,12 @@ class IrnTrainer:
         return net._trunk(ops.maxpool3s2(y))
 
     def heads(self, taps, keep=None):
-        """the two branches in train mode -> (edge_out [B,1,h,w], dp_out [B,2,h,w]), differentiable in the head parameters"""
-        return ops.irn_heads(taps, self.edge_params + self.dp_params, keep)
+        """the two branches in train mode -> (edge_out [B,1,h,w], dp_out [B,2,h,w]), differentiable in the head parameters.
+        keep: a dict that receives the forward's buffers (cat_e, cat6, cat7, a7: their signs are the ReLU masks).
+        As with the project's other arena-backed ops, the backward reads the parameters as they are THEN (autograd is not told of
+        an in-place update between forward and backward: do not step in between), and a parameter whose gradient has an arena
+        view gets it OVERWRITTEN, not accumulated: a second backward before the optimiser's step replaces the first."""
+        return IrnHeadsFn.apply(keep, *taps, *self.edge_params, *self.dp_params)
 
     def _label(self, label, hw):
         if not isinstance(label, torch.Tensor) or label.dtype != torch.uint8 or label.dim() != 3:

@@ -3592,7 +3592,7 @@ def irn_aff_losses(edge_out, dp_out, label, dirs, path_off, path_cells, radius=N
 
 
 # ------------------------------------------------------------------------ IRNet edge / displacement heads (training)
-# csrc/irntrain.hip (+ the float stem of csrc/irnnet.hip); the trainer is tris_amd/irn_train.py
+# csrc/irntrain.hip (+ the float stem of csrc/irnnet.hip); the trainer and the heads' autograd Function are tris_amd/irn_train.py
 def irn_stem_batch(img, wk, mean, invstd, gamma, beta):
     """img float32 [B,H,W,3], already normalised (zeros where the loader padded), wk [7,7,3,64] -> relu(bn(conv7x7 s2 p3)):
     [B,Ho,Wo,64]; no flip row"""
@@ -3646,125 +3646,6 @@ def irn_head_bwd(g, x, w, want_db=False, dw=None, db=None):
     ws = workspace(query("tris_irn_head_bwd_workspace_bytes", M, C, N))
     call("tris_irn_head_bwd_f32", P(g), P(x), C, P(w.contiguous()), P(dx), P(dw), P(db), M, C, N, P(ws), _stream())
     return dx, dw, db
-
-
-# (tap index, groups, upsample factor) of fc_edge1..5; of fc_dp1..5: IRNet/net/resnet50_irn.py:29-86
-_IRN_EDGE = ((0, 4, 1), (1, 4, 1), (2, 4, 2), (3, 4, 4), (4, 4, 4))
-_IRN_DP = ((0, 8, 1), (1, 16, 1), (2, 16, 1), (3, 16, 2), (4, 16, 2))
-IRN_HEAD_PARAMS = 39     # 5 x (conv, gamma, beta), fc_edge6 (weight, bias), 6 x (conv, gamma, beta), fc_dp7 (conv, gamma, beta, conv)
-
-
-def _wgrad_1x1(p, dt, x, needs):
-    """dW [N,K] = dt^T x for a 1x1 convolution weight, on the dense-product path; into the parameter's arena view if it has one"""
-    N, K = dt.shape[-1], x.shape[-1]
-    M = x.numel() // K
-    return _emit(p, lambda o: gemm(dt, x, o, N, K, M, N, K, K, True, False, mark=False), needs)
-
-
-def _dgrad_1x1(dt, w):
-    """dX [M,K] = dt w for a 1x1 convolution weight [N,K,1,1]"""
-    N = dt.shape[-1]
-    K = w.numel() // N
-    M = dt.numel() // N
-    dx = torch.empty(*dt.shape[:-1], K, dtype=torch.float32, device=dt.device)
-    gemm(dt, w, dx, M, K, N, N, K, K, False, False, w_b=True, w_bt=True)
-    return dx
-
-
-class IrnHeadsFn(torch.autograd.Function):
-    """Net.forward's two branches in train mode (IRNet/net/resnet50_irn.py:123-139; MeanShift is the identity there, :111-114):
-    taps x1..x5 (channels-last, detached) and the 39 head parameters -> edge_out [B,1,h,w], dp_out [B,2,h,w].  The Function owns
-    the concatenation buffers, the GroupNorm inputs and their statistics, and runs the backward in one fixed order; the only data
-    gradients formed are those of fc_dp7's and fc_dp6's inputs (no tap has one)."""
-
-    @staticmethod
-    def forward(ctx, keep, *args):
-        taps, prm = args[:5], args[5:]
-        if len(prm) != IRN_HEAD_PARAMS:
-            raise ValueError(f"irn_heads takes {IRN_HEAD_PARAMS} parameters, got {len(prm)}")
-        _chk(*taps, *prm)
-        taps = [t.contiguous() for t in taps]
-        dev = taps[0].device
-        B, h, w, _ = taps[1].shape
-        _, h3, w3, _ = taps[2].shape
-        saved = []      # (t, stats) of every GroupNorm, in forward order
-
-        def branch(x, conv, gamma, beta, G, scale, size, out, c_off):
-            t = linear(x, conv)
-            st = group_norm_stats(t, G, 1e-5)
-            saved.append((t, st))
-            return gn_apply_up(t, st, gamma, beta, G, scale, size, True, out, c_off)
-
-        cat_e = torch.empty(B, h, w, 160, dtype=torch.float32, device=dev)
-        for i, (tap, G, scale) in enumerate(_IRN_EDGE):
-            branch(taps[tap], *prm[3 * i:3 * i + 3], G, scale, (h, w), cat_e, 32 * i)
-        edge = irn_head(cat_e, prm[15].reshape(1, 160), prm[16])
-        d = prm[17:]
-        cat6 = torch.empty(B, h3, w3, 768, dtype=torch.float32, device=dev)
-        cat7 = torch.empty(B, h, w, 448, dtype=torch.float32, device=dev)
-        branch(taps[0], *d[0:3], 8, 1, (h, w), cat7, 0)
-        branch(taps[1], *d[3:6], 16, 1, (h, w), cat7, 64)
-        for j, i in enumerate((2, 3, 4)):
-            branch(taps[i], *d[3 * i:3 * i + 3], 16, _IRN_DP[i][2], (h3, w3), cat6, 256 * j)
-        branch(cat6, *d[15:18], 16, 2, (h, w), cat7, 192)
-        a7 = branch(cat7, *d[18:21], 16, 1, (h, w), None, 0)
-        dp = irn_head(a7, d[21].reshape(2, 256), None)
-        if keep is not None:
-            keep.update(cat_e=cat_e, cat6=cat6, cat7=cat7, a7=a7)
-        ctx.taps, ctx.prm, ctx.bufs, ctx.gn = taps, prm, (cat_e, cat6, cat7, a7), saved
-        return edge.reshape(B, 1, h, w), dp.permute(0, 3, 1, 2).contiguous()
-
-    @staticmethod
-    def backward(ctx, g_edge, g_dp):
-        taps, prm, (cat_e, cat6, cat7, a7), gn = ctx.taps, ctx.prm, ctx.bufs, ctx.gn
-        need = ctx.needs_input_grad[6:]
-        if any(ctx.needs_input_grad[1:6]):
-            raise RuntimeError("irn_heads: the taps are detached in the reference (resnet50_irn.py:117-121); they take no gradient")
-        B, h, w, _ = cat_e.shape
-        out = [None] * IRN_HEAD_PARAMS
-
-        def gn_conv(k, slot, d_out, buf, c_off, x, G, scale, dgrad=False):
-            """backward of branch number k of the forward (saved[k]) whose parameters are prm[slot : slot + 3]"""
-            t, st = gn[k]
-            sg, sb = _sink(prm[slot + 1]), _sink(prm[slot + 2])
-            dt, dgam, dbet = gn_up_bwd(d_out, buf, c_off, t, st, prm[slot + 1], G, scale, dgamma=sg, dbeta=sb)
-            out[slot] = _wgrad_1x1(prm[slot], dt, x, need[slot])
-            out[slot + 1] = dgam if sg is None and need[slot + 1] else None
-            out[slot + 2] = dbet if sb is None and need[slot + 2] else None
-            return _dgrad_1x1(dt, prm[slot]) if dgrad else None
-
-        # ---- the edge branch
-        if g_edge is None:
-            g_edge = torch.zeros(B, 1, h, w, dtype=torch.float32, device=cat_e.device)
-        sw, sb = _sink(prm[15]), _sink(prm[16])
-        d_cat, dw, db = irn_head_bwd(g_edge.contiguous(), cat_e, prm[15].reshape(1, 160), want_db=True, dw=sw, db=sb)
-        out[15] = dw.view_as(prm[15]) if sw is None and need[15] else None
-        out[16] = db if sb is None and need[16] else None
-        for i, (tap, G, scale) in enumerate(_IRN_EDGE):
-            gn_conv(i, 3 * i, d_cat, cat_e, 32 * i, taps[tap], G, scale)
-        # ---- the displacement branch: fc_dp7, then what fed its concatenation, then what fed fc_dp6's
-        if g_dp is None:
-            g_dp = torch.zeros(B, 2, h, w, dtype=torch.float32, device=cat_e.device)
-        sw = _sink(prm[38])
-        d_a7, dw3, _ = irn_head_bwd(g_dp.permute(0, 2, 3, 1).contiguous(), a7, prm[38].reshape(2, 256), dw=sw)
-        out[38] = dw3.view_as(prm[38]) if sw is None and need[38] else None
-        d_cat7 = gn_conv(11, 35, d_a7, a7, 0, cat7, 16, 1, dgrad=True)
-        gn_conv(5, 17, d_cat7, cat7, 0, taps[0], 8, 1)
-        gn_conv(6, 20, d_cat7, cat7, 64, taps[1], 16, 1)
-        d_cat6 = gn_conv(10, 32, d_cat7, cat7, 192, cat6, 16, 2, dgrad=True)
-        for j, i in enumerate((2, 3, 4)):
-            gn_conv(7 + j, 17 + 3 * i, d_cat6, cat6, 256 * j, taps[i], 16, _IRN_DP[i][2])
-        return (None,) * 6 + tuple(out)
-
-
-def irn_heads(taps, params, keep=None):
-    """taps: x1..x5 channels-last [B,H,W,C]; params: the 39 head parameters in the reference's trainable_parameters() order
-    (edge_layers, then dp_layers) -> (edge_out [B,1,h,w], dp_out [B,2,h,w]).  keep: a dict that receives the forward's buffers
-    (cat_e, cat6, cat7, a7: their signs are the ReLU masks).
-    As with the project's other arena-backed ops, the backward reads the parameters as they are THEN (autograd is not told of an
-    in-place update between forward and backward: do not step in between), and a parameter whose gradient has an arena view gets
-    it OVERWRITTEN, not accumulated: a second backward before the optimiser's step replaces the first."""
-    return IrnHeadsFn.apply(keep, *taps, *params)
 
 
 # ------------------------------------------------------------------------------------------ dense-CRF label pass (IRNet)
