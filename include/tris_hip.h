@@ -613,6 +613,27 @@ int tris_bce4_fwd_f32(const float* x1, const float* x2, const float* x3, const f
                       float* losses, double* workspace, void* stream);
 int tris_bce4_bwd_f32(const float* x1, const float* x2, const float* x3, const float* x4, const void* target, int target_f32,
                       const float* g, float* d1, float* d2, float* d3, float* d4, long n, void* stream);
+/* The Stage-2 step's whole loss with EMA consistency (train_stage2.py:258-269, 302-319) in one pass over the student maps x_k, the
+ * teacher maps e_k and the target: the four BCE terms as tris_bce4_fwd_f32 forms them plus l5 = sum_k mean((sigmoid(x_k) -
+ * sigmoid(e_k))^2) (sigmoid_mse_loss; the difference is squared in fp64), fp64 block partials, losses[6] = {l1 + l2 + l3 + l4 + l5,
+ * l1, l2, l3, l4, l5}.  x2..x4 may be NULL together with their e_k.  backward, one store per element: dx_k = (sigmoid(x) - t)(g[0] +
+ * g[k+1]) / n  [exactly tris_bce4_bwd_f32's value]  + 2 (sigmoid(x) - sigmoid(e)) s (1 - s) (g[0] + g[5]) / n,  s = sigmoid(x); e_k
+ * gets no gradient.  16-byte accesses when every base pointer is 16-byte aligned, the same element order with 4-byte accesses
+ * otherwise (same bits).  workspace: tris_seg_loss5_workspace_bytes(n). */
+long tris_seg_loss5_workspace_bytes(long n);
+int tris_seg_loss5_fwd_f32(const float* x1, const float* x2, const float* x3, const float* x4, const float* e1, const float* e2,
+                           const float* e3, const float* e4, const void* target, int target_f32, long n, float* losses,
+                           double* workspace, void* stream);
+int tris_seg_loss5_bwd_f32(const float* x1, const float* x2, const float* x3, const float* x4, const float* e1, const float* e2,
+                           const float* e3, const float* e4, const void* target, int target_f32, const float* g, float* d1, float* d2,
+                           float* d3, float* d4, long n, void* stream);
+/* The mean teacher's update (train_stage2.py:328-332; ema_pytorch's ema_param.lerp_(param, 1 - decay)): dst = lerp(dst, src, w) as
+ * torch defines it in fp32 -- w < 0.5 ? a + w (b - a) : b - (b - a)(1 - w), no fused multiply-add -- with w == 1 giving src and
+ * w == 0 leaving dst bit for bit.  16-byte accesses where dst and src share their offset inside a 16-byte line (the head and
+ * tail are peeled), 4-byte ones otherwise.  The table form does the same for `count` records {dst pointer, src pointer, n} (three
+ * 64-bit words each, device memory) in one launch: a workgroup walks whole records. */
+int tris_lerp_f32(float* dst, const float* src, long n, float w, void* stream);
+int tris_lerp_table_f32(const long* table, int count, float w, void* stream);
 /* Evaluation of a SIGNED map (Stage-2 logits; validate.py:179-191 as written): cam = bilinear(align_corners=True) / (max + 1e-5)
  * whatever the sign of the max (a negative max flips the sign), mask = cam > 1e-9, out_iu = {I, U, first arg-max of cam}.
  * tris_eval_post_f32 (the arg-max of the raw map) stays the Stage-1 entry.  map: S x S.  workspace >= 2049 + 4*1024 floats. */

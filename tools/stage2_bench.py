@@ -2,9 +2,13 @@
 both arithmetics of the dense products (h2, x3).  Seed-filled weights, synthetic images / tokens / pseudo targets.
 
     python tools/stage2_bench.py [--steps 20] [--warmup 5] [--batch 48] [--loader synthetic|dataloader|hbm] [--arith h2,x3]
+                                 [--model_ema]
 
 Prints one JSON line per arithmetic.  No target is set; the FLOP count it assumes is printed with it (forward, per image:
 the trunk + text encoder of Stage-1 plus the decoder and the three PixelAttentions, computed from the shapes).
+
+--model_ema: the step with EMA consistency training (tris_amd.ema.EMA built and bound as train_stage2.main does: the teacher's
+no-grad forward, ops.seg_loss5, and the teacher update every tenth step); the JSON line carries "model_ema": true and l5.
 
 --loader synthetic (default): one batch already on the device, stepped over and over -- what the step itself costs.
 --loader dataloader | hbm: the steps of train_stage2.train_one_epoch fed by the loader the trainer builds under TRIS_HBM_LOADER=0 |
@@ -75,6 +79,7 @@ def main():
     ap.add_argument("--batch", type=int, default=48)
     ap.add_argument("--loader", choices=["synthetic", "dataloader", "hbm"], default="synthetic")
     ap.add_argument("--arith", default="h2,x3", help="arithmetics of the dense products to run, comma separated")
+    ap.add_argument("--model_ema", action="store_true", help="EMA consistency training (the teacher forward, l5, the update)")
     ap.add_argument("--images", type=int, default=192, help="images of the synthetic dataset on disk (loader legs; >= 96)")
     a = ap.parse_args()
     if a.steps is None:
@@ -101,21 +106,28 @@ def main():
         ops.set_gemm_mode(mode)
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            model = TRIS(args).cuda().train()
+            model = TRIS(args).cuda()
         seed_fill(model.state_dict(), 1234)
+        ema = None
+        if a.model_ema:       # built where train_stage2.main builds it: before model.train() (its trunk stays in eval mode)
+            from tris_amd.ema import EMA
+            ema = EMA(model)
+        model.train()
         bb, hd = model.trainable_parameters()
         opt = FusedAdamW([{"params": bb, "lr": args.lr * args.lr_multi}, {"params": hd, "lr": args.lr}], lr=args.lr,
                          weight_decay=args.weight_decay)
+        if ema is not None:
+            ema.bind(opt)
         if loader is None:
             for _ in range(a.warmup):
-                train_step(model, opt, img, ids, tgt)
+                train_step(model, opt, img, ids, tgt, ema, ema is not None)
             torch.cuda.synchronize()
             t0 = time.time()
             for _ in range(a.steps):
-                last = train_step(model, opt, img, ids, tgt)
+                last = train_step(model, opt, img, ids, tgt, ema, ema is not None)
         else:
             def step(*batch):
-                return train_step(model, opt, *batch)
+                return train_step(model, opt, *batch, ema, ema is not None)
             _fed_steps(loader, a.warmup, step)
             torch.cuda.synchronize()
             t0 = time.time()
@@ -124,11 +136,12 @@ def main():
         dt = (time.time() - t0) / a.steps
         print(json.dumps({"metric": "stage2_train_img_per_s", "arith": mode, "value": round(a.batch / dt, 1),
                           "ms_per_step": round(1e3 * dt, 2), "batch": a.batch, "size": 320, "steps": a.steps,
-                          "loss": float(last[0]), "assumed_gflop_per_img_fwd_on_top_of_trunk_text": DECODER_GFLOP + PIXATTN_GFLOP,
+                          "loss": float(last[0]), "model_ema": ema is not None, "l5": float(last[5]) if ema is not None else 0.0,
+                          "assumed_gflop_per_img_fwd_on_top_of_trunk_text": DECODER_GFLOP + PIXATTN_GFLOP,
                           "loader": a.loader, "cache_build_s": None if build_s is None else round(build_s, 3),
                           "cache_bytes": cache_bytes}),
               flush=True)
-        del model, opt
+        del model, opt, ema
         torch.cuda.empty_cache()
     del loader      # (ends the DataLoader's workers before the dataset directory goes)
     if tmp is not None:

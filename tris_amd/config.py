@@ -27,6 +27,8 @@ assigning to it (`cfg.step_graph = "seg"`, `monkeypatch.setattr(cfg, "bn_pool", 
   hbm_loader         TRIS_HBM_LOADER           HBM-resident input pipeline (0: the reference's DataLoader)
   eval_group         TRIS_EVAL_GROUP           refs per batched evaluation group
   eval_boxes         TRIS_EVAL_BOXES           validate also reports HitM / box_mIOU / box_Acc (ops.eval_boxes per sentence; default 0: validate as it was, launch for launch)
+  stage2_ema         TRIS_STAGE2_EMA           train_stage2 accepts --model_ema: EMA consistency training with this stack's restatement of ema_pytorch.EMA
+                                               (tris_amd.ema; default 0: --model_ema is refused, and Stage-2 trains as it did, launch for launch)
   mbox_spin          TRIS_MBOX_SPIN            bound of the SyncBatchNorm mailbox spin (polls)
   syncbn_comm        TRIS_SYNCBN_COMM          "mailbox" | "c10d"
   ddp_check          TRIS_DDP_CHECK            NaN-poison check of the gradient reducer's release order
@@ -91,6 +93,7 @@ class _Config:
         self.hbm_loader = _flag("TRIS_HBM_LOADER", True)
         self.eval_group = max(1, int(e("TRIS_EVAL_GROUP", "16")))
         self.eval_boxes = _flag("TRIS_EVAL_BOXES", False)
+        self.stage2_ema = _flag("TRIS_STAGE2_EMA", False)
         self.mbox_spin = int(e("TRIS_MBOX_SPIN", "40000000"))
         self.syncbn_comm = e("TRIS_SYNCBN_COMM", "mailbox")
         self.ddp_check = e("TRIS_DDP_CHECK") == "1"

@@ -309,6 +309,171 @@ __global__ __launch_bounds__(256) void bce4_bwd_kernel(Heads4 h, Grads4 d, const
   }
 }
 
+// ------------------------------------------------------------------------------------------------ BCE + EMA consistency, 4 heads
+// One pass over x_k, the teacher map e_k and the target.  A thread owns whole quads (elements 4q .. 4q+3); VEC reads a quad as
+// one 16-byte word, !VEC (a base pointer that is not 16-byte aligned) as four 4-byte words: the element order, and with it every
+// sum, is the same.  The n % 4 last elements go to the first threads of block 0.
+template <bool VEC>
+__device__ __forceinline__ void quad_f32(const float* __restrict__ p, long q, float (&v)[4]) {
+  if (VEC) {
+    const float4 t = ld4(p + q * 4);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = p[q * 4 + j];
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void quad_target(const void* __restrict__ T, int t_f32, long q, float (&v)[4]) {
+  if (t_f32) {
+    quad_f32<VEC>(reinterpret_cast<const float*>(T), q, v);
+  } else if (VEC) {
+    const longlong2* p = reinterpret_cast<const longlong2*>(T) + q * 2;
+    const longlong2 a = p[0], b = p[1];
+    v[0] = (float)a.x; v[1] = (float)a.y; v[2] = (float)b.x; v[3] = (float)b.y;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (float)reinterpret_cast<const long*>(T)[q * 4 + j];
+  }
+}
+__device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }   // (bce4_bwd_kernel's expression)
+__device__ __forceinline__ void loss5_elem(float x, float e, float t, double& bce, double& mse) {
+  bce += (double)(fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x))));    // (bce4_fwd_kernel's expression)
+  const double d = (double)sigmoid_f32(x) - (double)sigmoid_f32(e);
+  mse += d * d;
+}
+// blockIdx.y = head; part[2 * head + {0: BCE, 1: consistency}][blk] = fp64 sums over the block's elements (0 for an absent head)
+template <bool VEC>
+__global__ __launch_bounds__(256) void loss5_fwd_kernel(Heads4 h, Heads4 ema, const void* __restrict__ T, int t_f32, long n,
+                                                        double* __restrict__ part) {
+  __shared__ double red0[256], red1[256];
+  const float* __restrict__ X = h.x[blockIdx.y];
+  const float* __restrict__ E = ema.x[blockIdx.y];
+  double s0 = 0.0, s1 = 0.0;
+  if (X != nullptr) {
+    const long n4 = n >> 2;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long)gridDim.x * 256) {
+      float x[4], e[4], t[4];
+      quad_f32<VEC>(X, q, x);
+      quad_f32<VEC>(E, q, e);
+      quad_target<VEC>(T, t_f32, q, t);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) loss5_elem(x[j], e[j], t[j], s0, s1);
+    }
+    const long i = n4 * 4 + threadIdx.x;
+    if (blockIdx.x == 0 && i < n) loss5_elem(X[i], E[i], target_at(T, t_f32, i), s0, s1);
+  }
+  red0[threadIdx.x] = s0;
+  red1[threadIdx.x] = s1;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) {
+      red0[threadIdx.x] += red0[threadIdx.x + o];
+      red1[threadIdx.x] += red1[threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    part[(long)(2 * blockIdx.y) * gridDim.x + blockIdx.x] = red0[0];
+    part[(long)(2 * blockIdx.y + 1) * gridDim.x + blockIdx.x] = red1[0];
+  }
+}
+// losses = {l1 + l2 + l3 + l4 + l5, l1, l2, l3, l4, l5}, l5 = the four consistency means summed (train_stage2.py:305-319)
+__global__ void loss5_finalize_kernel(const double* __restrict__ part, int nb, long n, float* __restrict__ losses) {
+  if (threadIdx.x != 0) return;
+  float l[4], m[4];
+  for (int k = 0; k < 4; ++k) {
+    double s = 0.0, c = 0.0;
+    for (int b = 0; b < nb; ++b) { s += part[(long)(2 * k) * nb + b]; c += part[(long)(2 * k + 1) * nb + b]; }
+    l[k] = (float)(s / (double)n);
+    m[k] = (float)(c / (double)n);
+    losses[1 + k] = l[k];
+  }
+  const float l5 = ((m[0] + m[1]) + m[2]) + m[3];
+  losses[5] = l5;
+  losses[0] = (((l[0] + l[1]) + l[2]) + l[3]) + l5;
+}
+// dX_k = (sigmoid(x) - t) * (g[0] + g[1 + k]) / n  [bce4_bwd_kernel's value]  + 2 (s - sigmoid(e)) s (1 - s) * (g[0] + g[5]) / n
+__device__ __forceinline__ float loss5_grad(float x, float e, float t, float gk, float gc) {
+#pragma clang fp contract(off)   // (the sum is not fused into the product before it: with e == x it is the BCE term's bits)
+  const float s = sigmoid_f32(x);
+  const float bce = (s - t) * gk;
+  const float c = ((2.0f * (s - sigmoid_f32(e))) * (s * (1.0f - s))) * gc;
+  return bce + c;
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void loss5_bwd_kernel(Heads4 h, Heads4 ema, Grads4 d, const void* __restrict__ T, int t_f32,
+                                                        const float* __restrict__ g, long n) {
+  const int k = blockIdx.y;
+  const float* __restrict__ X = h.x[k];
+  const float* __restrict__ E = ema.x[k];
+  float* __restrict__ D = d.d[k];
+  if (X == nullptr || D == nullptr) return;
+  const float gk = (g[0] + g[1 + k]) / (float)n, gc = (g[0] + g[5]) / (float)n;
+  const long n4 = n >> 2;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long)gridDim.x * 256) {
+    float x[4], e[4], t[4], o[4];
+    quad_f32<VEC>(X, q, x);
+    quad_f32<VEC>(E, q, e);
+    quad_target<VEC>(T, t_f32, q, t);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = loss5_grad(x[j], e[j], t[j], gk, gc);
+    if (VEC) {
+      st4(D + q * 4, make_float4(o[0], o[1], o[2], o[3]));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) D[q * 4 + j] = o[j];
+    }
+  }
+  const long i = n4 * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && i < n) D[i] = loss5_grad(X[i], E[i], target_at(T, t_f32, i), gk, gc);
+}
+
+inline int loss5_blocks(long n) {      // quads per block: 64 at least, 512 blocks per head at most
+  const long nb = ((n >> 2) + 63) / 64;
+  return (int)(nb < SEG_BLOCKS ? (nb < 1 ? 1 : nb) : SEG_BLOCKS);
+}
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ------------------------------------------------------------------------------------------------ lerp (the mean teacher's update)
+// torch's lerp in fp32, each operation rounded on its own; w == 0 / w == 1 return an operand untouched (signed zeros included)
+__device__ __forceinline__ float lerp_f32(float a, float b, float w) {
+#pragma clang fp contract(off)
+  if (w == 0.f) return a;
+  if (w == 1.f) return b;
+  const float d = b - a;
+  return w < 0.5f ? a + w * d : b - d * (1.0f - w);
+}
+// dst[0, n) by threads tid, tid + nt, ...: where dst and src sit at the same offset inside a 16-byte line, the elements up to
+// the next line are peeled, the body goes in 16-byte words and the rest one by one; otherwise everything goes one by one
+__device__ __forceinline__ void lerp_range(float* __restrict__ dst, const float* __restrict__ src, long n, float w, long tid,
+                                           long nt) {
+  const unsigned od = (unsigned)((reinterpret_cast<uintptr_t>(dst) >> 2) & 3), os = (unsigned)((reinterpret_cast<uintptr_t>(src) >> 2) & 3);
+  if (od != os) {
+    for (long i = tid; i < n; i += nt) dst[i] = lerp_f32(dst[i], src[i], w);
+    return;
+  }
+  long head = (4 - od) & 3;
+  if (head > n) head = n;
+  const long n4 = (n - head) >> 2, tail = head + n4 * 4;
+  for (long q = tid; q < n4; q += nt) {
+    const float4 a = ld4(dst + head + q * 4), b = ld4(src + head + q * 4);
+    st4(dst + head + q * 4, make_float4(lerp_f32(a.x, b.x, w), lerp_f32(a.y, b.y, w), lerp_f32(a.z, b.z, w), lerp_f32(a.w, b.w, w)));
+  }
+  if (tid < head) dst[tid] = lerp_f32(dst[tid], src[tid], w);
+  for (long i = tail + tid; i < n; i += nt) dst[i] = lerp_f32(dst[i], src[i], w);
+}
+__global__ __launch_bounds__(256) void lerp_kernel(float* __restrict__ dst, const float* __restrict__ src, long n, float w) {
+  lerp_range(dst, src, n, w, (long)blockIdx.x * 256 + threadIdx.x, (long)gridDim.x * 256);
+}
+struct LerpRec { float* dst; const float* src; long n; };
+__global__ __launch_bounds__(256) void lerp_table_kernel(const LerpRec* __restrict__ table, int count, float w) {
+  for (int r = blockIdx.x; r < count; r += gridDim.x) {
+    const LerpRec rec = table[r];
+    lerp_range(rec.dst, rec.src, rec.n, w, threadIdx.x, 256);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ signed evaluation
 // validate.py:179-191 as written: pred = bilinear_ac(map); pred /= max(pred) + 1e-5 (whatever its sign); mask = pred > 1e-9;
 // hit point = first arg-max of the NORMALISED map (np.argmax).  ws layout (floats): [0, 2*1024) max partials | [2048] max |
@@ -492,6 +657,64 @@ extern "C" int tris_bce4_bwd_f32(const float* x1, const float* x2, const float* 
   Heads4 h = {{x1, x2, x3, x4}};
   Grads4 d = {{d1, d2, d3, d4}};
   hipLaunchKernelGGL(bce4_bwd_kernel, dim3(seg_grid(n), 4), dim3(256), 0, (hipStream_t)stream, h, d, target, target_f32, g, n);
+  TRIS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" long tris_seg_loss5_workspace_bytes(long n) { return 8L * loss5_blocks(n) * (long)sizeof(double); }
+
+extern "C" int tris_seg_loss5_fwd_f32(const float* x1, const float* x2, const float* x3, const float* x4, const float* e1,
+                                      const float* e2, const float* e3, const float* e4, const void* target, int target_f32, long n,
+                                      float* losses, double* workspace, void* stream) {
+  if (n < 1 || x1 == nullptr || target == nullptr) return (int)hipErrorInvalidValue;
+  hipStream_t st = (hipStream_t)stream;
+  Heads4 h = {{x1, x2, x3, x4}}, ema = {{e1, e2, e3, e4}};
+  bool vec = aligned16(target);
+  for (int k = 0; k < 4; ++k) {
+    if ((h.x[k] == nullptr) != (ema.x[k] == nullptr)) return (int)hipErrorInvalidValue;
+    vec = vec && aligned16(h.x[k]) && aligned16(ema.x[k]);
+  }
+  const int nb = loss5_blocks(n);
+  if (vec) hipLaunchKernelGGL(loss5_fwd_kernel<true>, dim3(nb, 4), dim3(256), 0, st, h, ema, target, target_f32, n, workspace);
+  else hipLaunchKernelGGL(loss5_fwd_kernel<false>, dim3(nb, 4), dim3(256), 0, st, h, ema, target, target_f32, n, workspace);
+  TRIS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss5_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)workspace, nb, n, losses);
+  TRIS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tris_seg_loss5_bwd_f32(const float* x1, const float* x2, const float* x3, const float* x4, const float* e1,
+                                      const float* e2, const float* e3, const float* e4, const void* target, int target_f32,
+                                      const float* g, float* d1, float* d2, float* d3, float* d4, long n, void* stream) {
+  if (n < 1 || target == nullptr || g == nullptr) return (int)hipErrorInvalidValue;
+  Heads4 h = {{x1, x2, x3, x4}}, ema = {{e1, e2, e3, e4}};
+  Grads4 d = {{d1, d2, d3, d4}};
+  bool vec = aligned16(target);
+  for (int k = 0; k < 4; ++k) {
+    if (h.x[k] != nullptr && ema.x[k] == nullptr) return (int)hipErrorInvalidValue;
+    vec = vec && aligned16(h.x[k]) && aligned16(ema.x[k]) && aligned16(d.d[k]);
+  }
+  const dim3 grid(loss5_blocks(n), 4);
+  if (vec) hipLaunchKernelGGL(loss5_bwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, h, ema, d, target, target_f32, g, n);
+  else hipLaunchKernelGGL(loss5_bwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, h, ema, d, target, target_f32, g, n);
+  TRIS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tris_lerp_f32(float* dst, const float* src, long n, float w, void* stream) {
+  if (n < 0 || (n > 0 && (dst == nullptr || src == nullptr || dst == src))) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  const long g = (n / 4 + 255) / 256;        // one 16-byte word per thread, 2048 blocks at most
+  hipLaunchKernelGGL(lerp_kernel, dim3((unsigned)(g < 1 ? 1 : (g < 2048 ? g : 2048))), dim3(256), 0, (hipStream_t)stream, dst, src, n, w);
+  TRIS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tris_lerp_table_f32(const long* table, int count, float w, void* stream) {
+  if (count < 0 || (count > 0 && table == nullptr)) return (int)hipErrorInvalidValue;
+  if (count == 0) return 0;
+  hipLaunchKernelGGL(lerp_table_kernel, dim3((unsigned)(count < 2048 ? count : 2048)), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const LerpRec*>(table), count, w);
   TRIS_LAUNCH_CHECK();
   return 0;
 }

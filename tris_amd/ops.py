@@ -3180,6 +3180,103 @@ def bce(out, target):
     return Bce4Fn.apply(target, out, None, None, None)[1]
 
 
+class SegLoss5Fn(torch.autograd.Function):
+    """The Stage-2 step's loss with EMA consistency (train_stage2.py:302-319): the four BCE terms of Bce4Fn plus l5 = the four
+    sigmoid_mse_loss terms (:258-269) against the teacher's maps, in one pass -> losses[6] = (l1 + l2 + l3 + l4 + l5, l1, l2, l3,
+    l4, l5).  Heads 2..4 may be None together with their teacher maps.  The teacher maps get no gradient."""
+
+    @staticmethod
+    def forward(ctx, target, x1, x2, x3, x4, e1, e2, e3, e4):
+        xs = [None if x is None else x.contiguous() for x in (x1, x2, x3, x4)]
+        es = [None if e is None else e.detach().contiguous() for e in (e1, e2, e3, e4)]
+        _chk(target, *xs, *es)
+        if target.dtype not in (torch.int64, torch.float32):
+            target = target.float()
+        target = target.contiguous()
+        n = target.numel()
+        for k, (x, e) in enumerate(zip(xs, es)):
+            if (x is None) != (e is None):
+                raise ValueError(f"head {k + 1}: the student map and the teacher map must both be given or both be absent")
+            for t in (x, e):
+                if t is not None and (t.numel() != n or t.dtype != torch.float32):
+                    raise ValueError(f"head output {tuple(t.shape)} {t.dtype} does not match the target {tuple(target.shape)}")
+        kind = int(target.dtype == torch.float32)
+        losses = torch.empty(6, device=target.device, dtype=torch.float32)
+        ws = workspace(query("tris_seg_loss5_workspace_bytes", n))
+        call("tris_seg_loss5_fwd_f32", *[P(x) for x in xs], *[P(e) for e in es], P(target), kind, n, P(losses), P(ws), _stream())
+        ctx.kind = kind
+        ctx.save_for_backward(target, *xs, *es)
+        return losses
+
+    @staticmethod
+    def backward(ctx, g):
+        target, *rest = ctx.saved_tensors
+        xs, es = rest[:4], rest[4:]
+        g = g.contiguous()
+        ds = [None if x is None or not ctx.needs_input_grad[1 + k] else torch.empty_like(x) for k, x in enumerate(xs)]
+        call("tris_seg_loss5_bwd_f32", *[P(x) for x in xs], *[P(e) for e in es], P(target), ctx.kind, P(g), *[P(d) for d in ds],
+             target.numel(), _stream())
+        return (None, *ds, None, None, None, None)
+
+
+def seg_loss5(outs, ema_outs, target):
+    """outs / ema_outs: the student's and the teacher's four maps (trailing heads may be None in both) -> losses[6]"""
+    outs, ema_outs = list(outs), list(ema_outs)
+    if len(outs) != len(ema_outs) or not 1 <= len(outs) <= 4:
+        raise ValueError(f"{len(outs)} student maps against {len(ema_outs)} teacher maps")
+    pad = [None] * (4 - len(outs))
+    return SegLoss5Fn.apply(target, *outs, *pad, *ema_outs, *pad)
+
+
+def _lerp_dense(dst, src):
+    """dst and src cover the same elements in the same memory order (a dense tensor and its copy / its arena view)"""
+    if dst.dtype != torch.float32 or src.dtype != torch.float32:
+        raise TypeError(f"lerp needs fp32 tensors (got {dst.dtype}, {src.dtype})")
+    live = [i for i, n in enumerate(dst.shape) if n > 1]        # (the stride of a one-element dimension addresses nothing)
+    if dst.shape != src.shape or [dst.stride(i) for i in live] != [src.stride(i) for i in live]:
+        raise ValueError(f"lerp: {tuple(dst.shape)} / {dst.stride()} against {tuple(src.shape)} / {src.stride()}")
+    if not (dst.is_contiguous() or (dst.dim() == 4 and dst.is_contiguous(memory_format=torch.channels_last))):
+        raise ValueError(f"lerp needs dense tensors (shape {tuple(dst.shape)}, strides {dst.stride()})")
+    if dst.numel() and dst.data_ptr() == src.data_ptr():
+        raise ValueError("lerp: dst and src are the same memory")
+
+
+class LerpTable:
+    """device records {dst, src, n} of many tensor pairs: ema_update walks them in ONE launch, a workgroup per record.  A pair
+    longer than CHUNK elements becomes several records cut at multiples of CHUNK (whole 16-byte words: dst and src keep their
+    relative alignment), so that no workgroup walks megabytes alone.  Holds the tensors (the records are raw addresses)."""
+    CHUNK = 1 << 16
+
+    def __init__(self, pairs):
+        pairs = [(d, s) for d, s in pairs if d.numel() > 0]
+        for d, s in pairs:
+            _chk(d, s)
+            _lerp_dense(d, s)
+        self.pairs = pairs
+        rec = [[d.data_ptr() + 4 * o, s.data_ptr() + 4 * o, min(self.CHUNK, d.numel() - o)]
+               for d, s in pairs for o in range(0, d.numel(), self.CHUNK)]
+        self.records = torch.tensor(rec, dtype=torch.int64).reshape(len(rec), 3).to(pairs[0][0].device) if rec else None
+
+    def __len__(self):
+        return 0 if self.records is None else self.records.shape[0]
+
+
+def ema_update(what, w):
+    """dst <- lerp(dst, src, w) with torch's fp32 definition (w == 1: a copy, w == 0: nothing changes), the teacher update of the
+    reference's mean teacher (train_stage2.py:328-332).  what: a LerpTable -- one launch over all its records -- or a list of
+    (dst, src) pairs of flat buffers (the teacher's and the optimiser's parameter arenas): one launch each.  In-place without
+    telling torch: the caller bumps version counters where it matters (tris_amd.ema)."""
+    w = float(w)
+    if isinstance(what, LerpTable):
+        if len(what):
+            call("tris_lerp_table_f32", what.records.data_ptr(), len(what), w, _stream())
+        return
+    for dst, src in what:
+        _chk(dst, src)
+        _lerp_dense(dst, src)
+        call("tris_lerp_f32", P(dst), P(src), dst.numel(), w, _stream())
+
+
 def eval_post_signed(seg_map, target_u8):
     """validate.py:179-191 for one (image, sentence) of a SIGNED map (Stage-2 logits): normalised by max + 1e-5 whatever its sign.
     -> (iu int64[3] on device = I, U, first arg-max of the normalised map; cam [oH,oW])"""

@@ -12,8 +12,11 @@ the device per step.  The final evaluation of the train split reuses the trainin
 resized once per run.
 
 Single GPU, eager steps (the reference's Stage-2 script is single-GPU: --distributed raises).  EMA consistency training
-(--model_ema) needs `ema_pytorch`, which is not on this stack: it raises.  The aux ViT-B/32 the reference loads (:170) is never
-used without EMA and is not loaded.
+(--model_ema, :58-63, 302-312, 328-332) needs `ema_pytorch`, which is not on this stack: it raises, unless TRIS_STAGE2_EMA=1
+(cfg.stage2_ema) selects this stack's restatement of that package (tris_amd.ema): the mean teacher runs forward
+under no_grad on the same batch, four sigmoid-MSE terms join the loss as l5 (ops.seg_loss5) and the teacher is updated after every
+optimiser step.  The aux ViT-B/32 the reference loads (:170) is never read by its train_one_epoch, with or without EMA, and is not
+loaded.
 """
 import datetime
 import os
@@ -22,27 +25,43 @@ import time
 import torch
 
 from . import ops
+from .config import cfg
 from .train_stage1 import _logger, build_loader, setup_seed
 
 
 def _check_args(args):
     if getattr(args, "model_ema", False):
-        raise NotImplementedError("--model_ema: EMA consistency training needs the ema_pytorch package (train_stage2.py:22), "
-                                  "which is not on this stack; Stage-2 trains without EMA (l5 = 0)")
+        if not cfg.stage2_ema:
+            raise NotImplementedError("--model_ema: EMA consistency training needs the ema_pytorch package (train_stage2.py:22), "
+                                      "which is not on this stack; Stage-2 trains without EMA (l5 = 0).  TRIS_STAGE2_EMA=1 selects "
+                                      "this stack's restatement of it (tris_amd.ema)")
+        if getattr(args, "consistency_type", "mse") == "kl":
+            raise ValueError("--consistency_type kl with --model_ema: the reference passes the teacher's raw logits to F.kl_div as "
+                             "the target (train_stage2.py:286-288), so every negative logit gives NaN: there is nothing to reproduce")
     if getattr(args, "distributed", False):
         raise NotImplementedError("--distributed: the reference's Stage-2 script trains on a single GPU "
                                   "(scripts/train_stage2.sh); data-parallel Stage-2 is not implemented")
 
 
-def train_step(model, optimizer, img, word_ids, pseudo):
+def train_step(model, optimizer, img, word_ids, pseudo, model_ema=None, consistency=False):
     """forward -> the four BCE losses -> backward -> AdamW, bracketed as one h2 step (train_stage1._step_body).
-    -> device tensor losses[5] = (loss, l1, l2, l3, l4), detached (no host sync)"""
+    -> device tensor losses[5] = (loss, l1, l2, l3, l4), detached (no host sync).
+    model_ema (tris_amd.ema.EMA): its forward follows the student's under no_grad and it is updated behind the optimiser, all on
+    the one stream (the reference's torch.cuda.synchronize(), :327, orders nothing here); consistency: the loss is ops.seg_loss5
+    and -> losses[6] = (loss, l1, l2, l3, l4, l5)"""
+    if consistency and model_ema is None:
+        raise ValueError("consistency=True needs model_ema")
     ops.h2_begin_step()
     outs = model(img, word_ids)
-    losses = ops.bce4(outs, pseudo)
+    if model_ema is not None:
+        with torch.no_grad():
+            ema_outs = model_ema(img, word_ids)
+    losses = ops.seg_loss5(outs, ema_outs, pseudo) if consistency else ops.bce4(outs, pseudo)
     optimizer.zero_grad()
     losses[0].backward()
     optimizer.step()
+    if model_ema is not None:
+        model_ema.update()
     ops.h2_end_step()
     return losses.detach()
 
@@ -50,8 +69,9 @@ def train_step(model, optimizer, img, word_ids, pseudo):
 def train_one_epoch(train_loader, model, optimizer, epoch, local_rank, args, iteration=0, clip_model=None, model_ema=None):
     """The reference's signature and batch-dict contract (train_stage2.py:260); returns `iteration`."""
     _check_args(args)
-    if model_ema is not None:
-        raise NotImplementedError("model_ema: EMA consistency training is not implemented on this stack")
+    if model_ema is not None and not cfg.stage2_ema:
+        raise NotImplementedError("model_ema: EMA consistency training is off on this stack (TRIS_STAGE2_EMA=1 turns it on)")
+    consistency = model_ema is not None and bool(getattr(args, "model_ema", False))     # (train_stage2.py:302)
     model.train()
     num_steps = len(train_loader)
     t0 = time.time()
@@ -59,11 +79,11 @@ def train_one_epoch(train_loader, model, optimizer, epoch, local_rank, args, ite
         word_ids = samples["word_ids"].squeeze(1).cuda(local_rank, non_blocking=True)
         img = samples["img"].cuda(local_rank, non_blocking=True)
         pseudo = targets["pseudo_gt"].cuda(local_rank, non_blocking=True)
-        last = train_step(model, optimizer, img, word_ids, pseudo)
+        last = train_step(model, optimizer, img, word_ids, pseudo, model_ema, consistency)
         if idx % args.print_freq == 0 and local_rank == 0:
-            v = last.tolist()   # the only host sync, every print_freq steps
+            v = last.tolist() + [0.0]   # the only host sync, every print_freq steps (without EMA l5 is the reference's constant 0)
             print(f"Train:[{epoch:2d}/{args.epoch}][{idx:4d}/{num_steps}] | lr {optimizer.param_groups[0]['lr']:.6f} || "
-                  f"loss: {v[0]:.4f} | l1: {v[1]:.4f} | l2: {v[2]:.4f} | l3: {v[3]:.4f} | l4: {v[4]:.4f} | l5: 0.0000 | "
+                  f"loss: {v[0]:.4f} | l1: {v[1]:.4f} | l2: {v[2]:.4f} | l3: {v[3]:.4f} | l4: {v[4]:.4f} | l5: {v[5]:.4f} | "
                   f"time/step: {(time.time() - t0) / (idx + 1):.4f}", flush=True)
         iteration += 1
     print(f"EPOCH {epoch} training takes {datetime.timedelta(seconds=int(time.time() - t0))}", flush=True)
@@ -90,6 +110,13 @@ def main(args, tokenizer=None):
     local_rank = 0
     log = _logger(args, local_rank)
     model = TRIS(args).cuda()
+    model_ema = None
+    if args.model_ema:
+        # where the reference builds it (:58-63): before model.train() and before any checkpoint is loaded.  The copy keeps the modes
+        # of this moment for good -- root and decoder in train mode, the CLIP backbone in eval mode (clip's build_model returns
+        # .eval()) -- so the teacher's trunk runs on running statistics and its decoder BatchNorms on batch statistics
+        from .ema import EMA
+        model_ema = EMA(model)
     param_groups = model.trainable_parameters()
     model.train()
     log.info(f"number of params: {sum(p.numel() for p in model.parameters() if p.requires_grad) / 1e6:.2f}M")
@@ -104,6 +131,8 @@ def main(args, tokenizer=None):
         {"params": param_groups[0], "lr": args.lr * args.lr_multi, "weight_decay": args.weight_decay},
         {"params": param_groups[1], "lr": args.lr, "weight_decay": args.weight_decay},
     ], lr=args.lr, weight_decay=args.weight_decay)
+    if model_ema is not None:
+        model_ema.bind(optimizer)
 
     if args.resume and args.eval:
         load_checkpoint(args, model, optimizer, None, log)
@@ -135,7 +164,7 @@ def main(args, tokenizer=None):
     iteration, train_time, start = 0, 0.0, time.time()
     for epoch in range(args.start_epoch, args.epoch):
         t0 = time.time()
-        iteration = train_one_epoch(train_loader, model, optimizer, epoch, local_rank, args, iteration)
+        iteration = train_one_epoch(train_loader, model, optimizer, epoch, local_rank, args, iteration, model_ema=model_ema)
         scheduler.step()                  # once per EPOCH, as train_stage2.py:192
         torch.cuda.synchronize()
         train_time += time.time() - t0
