@@ -655,6 +655,26 @@ long tris_eval_boxes_workspace_bytes(int H, int W);
 int tris_eval_boxes_f32(const float* cam, const unsigned char* target, int H, int W, const int* gt_box, const long* iu, int* record,
                         int* boxes_out, void* workspace, void* stream);
 
+/* ---- ReferIt evaluation (csrc/referit.hip; validate_referit.py, dataset/Dataset_referit.py), DESIGN section 17 -------------
+ * Targets of the K sentences of one image from run lengths (dataset/Dataset_referit.py:141-144: cocomask.decode(rle), np.sum(axis=2),
+ * astype(uint8)).  ends int32: for every segment the inclusive prefix sums of its counts, i.e. the column-major position where each
+ * run ends (non-decreasing, <= H*W); seg_off int64 [segments + 1]: the slice of `ends` of each segment; ranges int32 [K][2] =
+ * {first segment, one past the last} of sentence k; all in device memory.  out uint8 [K][H][W] row-major: out[k][y][x] = the number
+ * of segments of sentence k whose run holding position x*H + y has an odd index -- a first count of 0, zero-length runs, counts
+ * that stop short of H*W (the rest is background), a sentence without segments (zeros) and overlapping segments (values above 1)
+ * included.  At most 255 segments per sentence (the caller checks), H*W <= 2^24, else hipErrorInvalidValue. */
+int tris_rle_decode_sum_u8(const int* ends, const long* seg_off, const int* ranges, int K, int H, int W, unsigned char* out,
+                           void* stream);
+/* K sentences of one image scored in one call (validate_referit.py:160-171, 104-118): maps float32 [K][S][S], targets uint8
+ * [K][oH][oW] (counts: a pixel is target where the count is != 0, as logical_and / logical_or read it), cams float32 [K][oH][oW]
+ * or NULL.  records int64 [K][4] = {I, U, first arg-max of cam, target value at that arg-max}.  Per sentence the first three
+ * words and cams[k] are bit for bit what tris_eval_post_f32 (is_signed = 0) or tris_eval_post_signed_f32 (is_signed = 1) gives
+ * on (targets[k] != 0); the fourth is the raw count, which validate_referit.py:111-113 compares with 1.  Four launches whatever
+ * K is.  workspace: tris_eval_post_group_workspace_bytes(K) bytes. */
+long tris_eval_post_group_workspace_bytes(int K);
+int tris_eval_post_group_f32(const float* maps, int S, const unsigned char* targets, int K, int oH, int oW, float* cams, long* records,
+                             int is_signed, float* workspace, void* stream);
+
 /* ---- Instance-mask synthesis (csrc/insseg.hip; irn.py): the post-network half of IRNet's make_ins_seg_labels --------------
  * (response map, edge map [h,w], displacement field [2,h,w]) -> instance masks, the pseudo labels Stage 2 trains on.  Reference
  * lines are those of IRNet/step_refer/make_ins_seg_labels.py ("labels.py") and IRNet/misc/indexing.py.  f32 on the vector ALU;

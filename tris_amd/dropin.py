@@ -42,12 +42,14 @@ ALIASES = {
     "loss": "tris_amd.loss",
     "loss.clip_loss": "tris_amd.loss.clip_loss",
     "validate": "tris_amd.validate",
+    "validate_referit": "tris_amd.validate_referit",
     "args": "tris_amd.args",
     "utils": "tris_amd.utils",
     "utils.util": "tris_amd.utils.util",
     "dataset": "tris_amd.dataset",
     "dataset.ReferDataset": "tris_amd.dataset.ReferDataset",
     "dataset.transform": "tris_amd.dataset.transform",
+    "dataset.Dataset_referit": "tris_amd.dataset.Dataset_referit",
     "dataset.refer": "tris_amd.dataset.refer",
     "train_stage1": "tris_amd.train_stage1",
     "train_stage2": "tris_amd.train_stage2",

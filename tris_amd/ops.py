@@ -3349,6 +3349,68 @@ def eval_boxes(cam, target_u8, gt_box, iu, return_boxes=False):
     return record, out
 
 
+# ------------------------------------------------------------------------------------------ ReferIt evaluation (csrc/referit.hip)
+def rle_decode_sum_arena(ends, seg_off, ranges, H, W, out=None):
+    """targets of the K sentences of one image from a device arena (dataset/rle_arena.py: RleArena.to): ends int32, seg_off int64,
+    ranges int32 [K,2] -> uint8 [K,H,W] = cocomask.decode(...).sum(2).astype(uint8) of every sentence, one launch.  The arena's
+    builder has checked the run lengths; nothing here reads them back."""
+    for t, dt in ((ends, torch.int32), (seg_off, torch.int64), (ranges, torch.int32)):
+        if not t.is_cuda:
+            raise NoGpuError("tris_amd ops run on MI355X only (got a CPU tensor); there is no CPU fallback")
+        if t.dtype != dt:
+            raise TypeError(f"expected {dt}, got {t.dtype}")
+    if ranges.dim() != 2 or ranges.shape[1] != 2:
+        raise ValueError(f"ranges is [K,2], got {tuple(ranges.shape)}")
+    if H < 1 or W < 1 or H * W > (1 << 24):
+        raise ValueError(f"rle_decode_sum: {H}x{W} is empty or beyond 2^24 pixels")
+    K = ranges.shape[0]
+    if out is None:
+        out = torch.empty(K, H, W, dtype=torch.uint8, device=ranges.device)
+    else:
+        _chk_u8(out)
+        assert tuple(out.shape) == (K, H, W) and out.is_contiguous()
+    if K:
+        call("tris_rle_decode_sum_u8", P(ends.contiguous()), P(seg_off.contiguous()), P(ranges.contiguous()), K, H, W, P(out),
+             _stream())
+    return out
+
+
+def rle_decode_sum(sentences, H, W, names=None, device="cuda"):
+    """sentences: per sentence the list of its RLE dicts (counts as a list or a compressed string) -> uint8 [K,H,W] on the device.
+    Refused before any launch, naming the sentence (names[k], or its index): a negative count, counts that sum past H*W, more than
+    255 segments for one sentence, H*W > 2^24."""
+    from .dataset.rle_arena import RleArena
+    arena = RleArena()
+    ranges = [arena.add_sentence(s, H, W, str(names[k]) if names is not None else f"sentence {k}") for k, s in enumerate(sentences)]
+    if not torch.cuda.is_available():
+        raise NoGpuError("tris_amd ops run on MI355X only; there is no CPU fallback")
+    ends, seg_off = arena.to(device)
+    rng = torch.tensor(ranges, dtype=torch.int32).reshape(-1, 2).to(device)
+    return rle_decode_sum_arena(ends, seg_off, rng, H, W)
+
+
+def eval_post_group(maps, targets_u8, signed=False, cams=True):
+    """validate_referit.py:160-171 for the K sentences of one image in one call: maps [K,S,S] (or [K,1,S,S]), targets_u8 [K,oH,oW]
+    counts -> (records int64 [K,4] on the device = I, U, first arg-max of cam, target count at the arg-max; cams [K,oH,oW], None
+    with cams=None / False).  records[k,:3] and cams[k] are bit for bit eval_post / eval_post_signed of sentence k on targets != 0."""
+    _chk(maps, targets_u8)
+    if maps.dtype != torch.float32 or targets_u8.dtype != torch.uint8:
+        raise TypeError("eval_post_group takes (float32 maps, uint8 targets)")
+    K, S = maps.shape[0], maps.shape[-1]
+    if maps.shape[-2] != S or maps.numel() != K * S * S:
+        raise ValueError(f"eval_post_group takes K square maps, got {tuple(maps.shape)}")
+    if targets_u8.dim() != 3 or targets_u8.shape[0] != K:
+        raise ValueError(f"eval_post_group: {K} maps and targets {tuple(targets_u8.shape)}")
+    oH, oW = targets_u8.shape[-2:]
+    records = torch.empty(K, 4, device=maps.device, dtype=torch.int64)
+    cam = torch.empty(K, oH, oW, device=maps.device, dtype=torch.float32) if cams else None
+    if K:
+        ws = workspace(query("tris_eval_post_group_workspace_bytes", K))
+        call("tris_eval_post_group_f32", P(maps.contiguous()), S, P(targets_u8.contiguous()), K, oH, oW, P(cam), P(records),
+             1 if signed else 0, P(ws), _stream())
+    return records, cam
+
+
 # ------------------------------------------------------------------------------------- instance-mask synthesis (IRNet tail)
 # csrc/insseg.hip; the public functions with the reference's names are in tris_amd/irn.py
 def _chk_t(t, dtype):
