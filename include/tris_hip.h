@@ -675,6 +675,26 @@ long tris_eval_post_group_workspace_bytes(int K);
 int tris_eval_post_group_f32(const float* maps, int S, const unsigned char* targets, int K, int oH, int oW, float* cams, long* records,
                              int is_signed, float* workspace, void* stream);
 
+/* ---- Heat-map overlay of single-image inference (csrc/overlay.hip; demo.py:28-48, 94-96), DESIGN section 18 ---------------
+ * The K response maps of ONE image painted in one call, two launches whatever K is.  For sentence k and output pixel (y, x):
+ * u = max(bilinear(maps[k], align_corners=True)(y, x), 0); lo, hi = min, max of u over the H x W OUTPUT grid;
+ * TRIS_PAINT_MINMAX: n = (u - lo) / (hi - lo + 1e-5f) (get_norm_cam);  TRIS_PAINT_UNIT: n = min(u, 1) (maps already in [0, 1]);
+ * i = (int)(n * 255) by truncation (np.uint8), c = lut[i]; heat = (3 c + 2 image + 2) / 5 per channel in integers -- cv2's
+ * addWeighted(.6, .4) with round-to-nearest -- or c where image is NULL (visualize_cam's original=None).  norm (may be NULL) gets n;
+ * range[k] = {lo, hi}; argmax[k] = raster index of the first pixel whose u equals hi (np.argmax).  The colour table is data: 256
+ * RGB rows.  Sh, Sw, H, W >= 1; K = 0 succeeds without a launch; K <= 65535.  heat 4-byte, norm 16-byte, workspace 8-byte
+ * aligned, else hipErrorInvalidValue.  A sentence's outputs do not depend on the K it shares the call with.  No host
+ * synchronisation, no allocation: the call can be captured.  workspace: tris_cam_paint_workspace_bytes(K, H, W) bytes. */
+#define TRIS_PAINT_MINMAX 0
+#define TRIS_PAINT_UNIT 1
+long tris_cam_paint_workspace_bytes(int K, int H, int W);
+int tris_cam_paint_f32(const float* maps /*[K][Sh][Sw]*/, int K, int Sh, int Sw,
+                       const unsigned char* image /*[H][W][3] or NULL*/, int H, int W,
+                       const unsigned char* lut /*[256][3]*/, int mode,
+                       unsigned char* heat /*[K][H][W][3]*/, float* norm /*[K][H][W] or NULL*/,
+                       float* range /*[K][2] = {min, max} after the clamp*/, long* argmax /*[K]*/,
+                       void* workspace, void* stream);
+
 /* ---- Instance-mask synthesis (csrc/insseg.hip; irn.py): the post-network half of IRNet's make_ins_seg_labels --------------
  * (response map, edge map [h,w], displacement field [2,h,w]) -> instance masks, the pseudo labels Stage 2 trains on.  Reference
  * lines are those of IRNet/step_refer/make_ins_seg_labels.py ("labels.py") and IRNet/misc/indexing.py.  f32 on the vector ALU;

@@ -64,5 +64,19 @@ __device__ __forceinline__ float sample_ac(const float* __restrict__ m, int S, i
   float top = v00 + wx * (v01 - v00), bot = v10 + wx * (v11 - v10);
   return top + wy * (bot - top);
 }
+// The same expressions for an Sh x Sw map (overlay.hip), with contraction off: the source position stays a float32 product of its
+// own, so position and weight are exactly the float32 values F.interpolate defines and the weight's subtraction is exact.  Fused
+// into that subtraction (what the compiler does by default), the product would move the weight by up to half an ulp of the POSITION.
+__device__ __forceinline__ float sample_ac_rect(const float* __restrict__ m, int Sh, int Sw, int oH, int oW, int oy, int ox) {
+#pragma clang fp contract(off)
+  float sy = oH > 1 ? (float)(Sh - 1) / (float)(oH - 1) : 0.f, sx = oW > 1 ? (float)(Sw - 1) / (float)(oW - 1) : 0.f;
+  float fy = sy * (float)oy, fx = sx * (float)ox;
+  int y0 = min((int)fy, Sh - 1), x0 = min((int)fx, Sw - 1);
+  int y1 = y0 + (y0 < Sh - 1 ? 1 : 0), x1 = x0 + (x0 < Sw - 1 ? 1 : 0);
+  float wy = fy - (float)y0, wx = fx - (float)x0;
+  float v00 = m[y0 * Sw + x0], v01 = m[y0 * Sw + x1], v10 = m[y1 * Sw + x0], v11 = m[y1 * Sw + x1];
+  float top = v00 + wx * (v01 - v00), bot = v10 + wx * (v11 - v10);
+  return top + wy * (bot - top);
+}
 
 }  // namespace

@@ -3411,6 +3411,65 @@ def eval_post_group(maps, targets_u8, signed=False, cams=True):
     return records, cam
 
 
+# ------------------------------------------------------------------------------------- heat-map overlay (csrc/overlay.hip)
+_PAINT_LUT = {}
+
+
+def cam_paint(maps, image_u8=None, lut=None, mode="minmax", want_norm=False, size=None):
+    """demo.py:28-48, 94-96 for the K sentences of one image in one call (two launches): maps float32 [K,Sh,Sw] (or [K,1,Sh,Sw]),
+    image_u8 uint8 [H,W,3] RGB or None (then `size` = (H, W), default the maps' own), lut uint8 [256,3] (default
+    tris_amd.predict.JET), mode "minmax" (get_norm_cam on the resized, clamped map) or "unit" (maps already in [0, 1]).
+    -> (heat uint8 [K,H,W,3], norm float32 [K,H,W] | None, range float32 [K,2] = min, max after the clamp, argmax int64 [K] = raster
+    index of the first maximum), all on the device; nothing is synchronised.  Arguments must be contiguous: a strided view is
+    refused by name, not copied."""
+    if mode not in ("minmax", "unit"):
+        raise ValueError(f"cam_paint: mode is 'minmax' or 'unit', got {mode!r}")
+    if not torch.is_tensor(maps):
+        raise TypeError("cam_paint: maps is a float32 device tensor")
+    if lut is None and maps.is_cuda:
+        lut = _PAINT_LUT.get(maps.device)
+        if lut is None:
+            from .predict import JET
+            lut = _PAINT_LUT[maps.device] = torch.from_numpy(JET.copy()).to(maps.device)
+    for name, t, dt in (("maps", maps, torch.float32), ("image_u8", image_u8, torch.uint8), ("lut", lut, torch.uint8)):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise NoGpuError(f"tris_amd ops run on MI355X only (cam_paint: {name} is not a device tensor); there is no CPU fallback")
+        if t.dtype != dt:
+            raise TypeError(f"cam_paint: {name} must be {dt}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"cam_paint: {name} must be contiguous")
+    if maps.dim() == 4 and maps.shape[1] == 1:
+        maps = maps.reshape(maps.shape[0], maps.shape[2], maps.shape[3])
+    if maps.dim() != 3 or maps.shape[1] < 1 or maps.shape[2] < 1:
+        raise ValueError(f"cam_paint: maps is [K,Sh,Sw], got {tuple(maps.shape)}")
+    K, Sh, Sw = maps.shape
+    if tuple(lut.shape) != (256, 3):
+        raise ValueError(f"cam_paint: lut is [256,3], got {tuple(lut.shape)}")
+    if image_u8 is not None:
+        if image_u8.dim() != 3 or image_u8.shape[2] != 3:
+            raise ValueError(f"cam_paint: image_u8 is [H,W,3], got {tuple(image_u8.shape)}")
+        H, W = image_u8.shape[:2]
+        if size is not None and tuple(size) != (H, W):
+            raise ValueError(f"cam_paint: size {tuple(size)} and image_u8 {tuple(image_u8.shape)} differ")
+    else:
+        H, W = (Sh, Sw) if size is None else (int(size[0]), int(size[1]))
+    if H < 1 or W < 1 or K > 65535:
+        raise ValueError(f"cam_paint: {K} maps to {H}x{W}")
+    dev = maps.device
+    heat = torch.empty(K, H, W, 3, dtype=torch.uint8, device=dev)
+    norm = torch.empty(K, H, W, dtype=torch.float32, device=dev) if want_norm else None
+    rng = torch.empty(K, 2, dtype=torch.float32, device=dev)
+    arg = torch.empty(K, dtype=torch.int64, device=dev)
+    if K:
+        ws = workspace(query("tris_cam_paint_workspace_bytes", K, H, W) + 256)
+        base = (ws.data_ptr() + 255) & ~255
+        call("tris_cam_paint_f32", P(maps), K, Sh, Sw, P(image_u8), H, W, P(lut), CONSTS["TRIS_PAINT_UNIT" if mode == "unit" else
+             "TRIS_PAINT_MINMAX"], P(heat), P(norm), P(rng), P(arg), base, _stream())
+    return heat, norm, rng, arg
+
+
 # ------------------------------------------------------------------------------------- instance-mask synthesis (IRNet tail)
 # csrc/insseg.hip; the public functions with the reference's names are in tris_amd/irn.py
 def _chk_t(t, dtype):
