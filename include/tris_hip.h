@@ -675,6 +675,29 @@ long tris_eval_post_group_workspace_bytes(int K);
 int tris_eval_post_group_f32(const float* maps, int S, const unsigned char* targets, int K, int oH, int oW, float* cams, long* records,
                              int is_signed, float* workspace, void* stream);
 
+/* ---- REFER polygon targets as run-length arenas (csrc/polymask.hip; dataset/refer.py:279-291 getMask, dataset/ReferDataset.py
+ * load_mask), DESIGN section 19 ------------------------------------------------------------------------------------------------
+ * cocomask.frPyObjects of P polygons on the device (dataset/refer.py:283: mask.frPyObjects(ann['segmentation'], h, w)), bit for
+ * bit what dataset/cocomask.py:13-54 gives before its zero-run merge.  verts int32 [V][2] = the x5 upsampled vertices
+ * (X, Y) = (int(5 x + 0.5), int(5 y + 0.5)) formed by the host in double arithmetic (cocomask.py:18-19), |X|, |Y| <= 2^20;
+ * poly_off int64 [P + 1]: the vertex slice of each polygon (an empty slice marks a segment the host fills itself: n_runs = 1,
+ * nothing emitted); hw int32 [P][2] = {H, W} of each polygon's canvas, H*W <= 2^24.  All in device memory; the host has checked
+ * the bounds (dataset/poly_arena.py), nothing here reads them back.
+ * tris_poly_count_runs: n_runs int32 [P] = the polygon's kept column crossings + 1 (the closing H*W).
+ * tris_poly_emit_runs: seg_off int64 [P + 1] = the exclusive scan of n_runs; ends[seg_off[p] .. seg_off[p + 1]) = the column-major
+ * positions xc*H + yc of the crossings and H*W, sorted ascending with duplicates kept (a duplicate pair is a zero-length run, which
+ * tris_rle_decode_sum_u8 reads as cocomask's merge loop does): the (ends, seg_off) arena of tris_rle_decode_sum_u8.  Slices of up to
+ * tris_poly_sort_capacity() ends are sorted in LDS, longer ones in place in global memory; one workgroup per polygon, P <= 2^31 - 1. */
+int tris_poly_sort_capacity(void);
+int tris_poly_count_runs(const int* verts, const long* poly_off, const int* hw, int P, int* n_runs, void* stream);
+int tris_poly_emit_runs(const int* verts, const long* poly_off, const int* hw, const long* seg_off, int P, int* ends, void* stream);
+/* Training target of one ref from its runs (dataset/ReferDataset.py load_mask: annot[ref_mask == 1] = 1, then dataset/transform.py:32
+ * Image.NEAREST): out uint8 [Hout][Wout], out[y][x] = 1 where exactly one of the segments seg_lo .. seg_hi - 1 covers source pixel
+ * (yidx[y], xidx[x]) of the H x W canvas, else 0 (index < 0 -> 0), with the index tables of tris_gather2d_u8.  The full-size mask is
+ * never formed.  seg_hi - seg_lo <= 255, H*W <= 2^24, else hipErrorInvalidValue. */
+int tris_rle_target_nearest_u8(const int* ends, const long* seg_off, int seg_lo, int seg_hi, int H, int W, const int* yidx,
+                               const int* xidx, int Hout, int Wout, unsigned char* out, void* stream);
+
 /* ---- Heat-map overlay of single-image inference (csrc/overlay.hip; demo.py:28-48, 94-96), DESIGN section 18 ---------------
  * The K response maps of ONE image painted in one call, two launches whatever K is.  For sentence k and output pixel (y, x):
  * u = max(bilinear(maps[k], align_corners=True)(y, x), 0); lo, hi = min, max of u over the H x W OUTPUT grid;

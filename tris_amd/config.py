@@ -29,6 +29,9 @@ assigning to it (`cfg.step_graph = "seg"`, `monkeypatch.setattr(cfg, "bn_pool", 
   eval_boxes         TRIS_EVAL_BOXES           validate also reports HitM / box_mIOU / box_Acc (ops.eval_boxes per sentence; default 0: validate as it was, launch for launch)
   stage2_ema         TRIS_STAGE2_EMA           train_stage2 accepts --model_ema: EMA consistency training with this stack's restatement of ema_pytorch.EMA
                                                (tris_amd.ema; default 0: --model_ema is refused, and Stage-2 trains as it did, launch for launch)
+  poly_targets       TRIS_POLY_TARGETS         HbmReferCache builds the RefCOCO/+/g targets on the device from the polygons (dataset/poly_arena.py, csrc/polymask.hip):
+                                               no host rasterisation, no full-size mask upload, evaluation masks kept as run ends and decoded per ref
+                                               (default 0: the cache is built as it was, launch for launch)
   mbox_spin          TRIS_MBOX_SPIN            bound of the SyncBatchNorm mailbox spin (polls)
   syncbn_comm        TRIS_SYNCBN_COMM          "mailbox" | "c10d"
   ddp_check          TRIS_DDP_CHECK            NaN-poison check of the gradient reducer's release order
@@ -94,6 +97,7 @@ class _Config:
         self.eval_group = max(1, int(e("TRIS_EVAL_GROUP", "16")))
         self.eval_boxes = _flag("TRIS_EVAL_BOXES", False)
         self.stage2_ema = _flag("TRIS_STAGE2_EMA", False)
+        self.poly_targets = _flag("TRIS_POLY_TARGETS", False)
         self.mbox_spin = int(e("TRIS_MBOX_SPIN", "40000000"))
         self.syncbn_comm = e("TRIS_SYNCBN_COMM", "mailbox")
         self.ddp_check = e("TRIS_DDP_CHECK") == "1"

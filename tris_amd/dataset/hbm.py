@@ -23,6 +23,10 @@ training batches, gathered by the same ref index vector as "target".
 Evaluation datasets never read pseudo files, whatever their `pseudo_path`: the reference hands its evaluation datasets the
 same directory (validate.py:64), their items carry no pseudo target, and files for those refs do not exist.
 
+`cfg.poly_targets` (TRIS_POLY_TARGETS, default 0): the targets are built on the device from the annotation polygons
+(dataset/poly_arena.py, csrc/polymask.hip) -- no ReferDataset.load_mask, no full-size mask upload; training rows are decoded at
+the NEAREST resize's source positions, evaluation keeps the run ends and decodes a ref per batch.  Batches are bit-identical.
+
 `images_from=`: a second cache over the same images at the same size (the train split evaluated after Stage-2 training)
 takes the decoded and resized images of the first instead of decoding them again.
 """
@@ -32,6 +36,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..config import cfg
 from .transform import normalize_table
 
 
@@ -99,10 +104,14 @@ class HbmReferCache:
         for i in range(n):
             if self.slot_of[i] >= n_donor:      # (rows below n_donor are the donor's: already decoded)
                 first_ref.setdefault(int(self.slot_of[i]), i)
+        self.arena = None                 # cfg.poly_targets, evaluation: the refs' run ends (dataset/poly_arena.py: DeviceArena)
+        poly = cfg.poly_targets
         with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
             for s, img in zip(first_ref, pool.map(ds.load_image, first_ref.values())):
                 ops.resample_u8(torch.from_numpy(np.asarray(img).copy()).to(dev), S, S, out=self.images[s])
-            for i, (annot, bbox) in enumerate(pool.map(ds.load_mask, range(n))):
+            if poly:
+                boxes, sizes, paths, self.files = self._poly_targets(recs)
+            for i, (annot, bbox) in enumerate(pool.map(ds.load_mask, range(0 if poly else n))):
                 m = torch.from_numpy(np.asarray(annot).copy()).to(dev)
                 if train:
                     ops.resize_nearest_u8(m, S, S, out=self.targets[i])
@@ -128,6 +137,36 @@ class HbmReferCache:
         self._index_tokens(n)
         torch.cuda.synchronize(dev)
 
+    def _poly_targets(self, recs):
+        """cfg.poly_targets: the refs' polygons -> run ends on the device (dataset/poly_arena.py), once for the split; no
+        ReferDataset.load_mask, no full-size mask.  Training: targets[i] decoded at the positions the NEAREST resize reads, the arena
+        dropped afterwards.  Evaluation: the arena is kept and eval_batch decodes a ref when it is asked for.
+        -> (boxes, sizes, paths, files) as load_mask and the build loop derive them from the annotation records"""
+        from .poly_arena import PolyArena
+        ds, S, refer = self.dataset, self.size, self.dataset.refer
+        arena = PolyArena()
+        boxes, sizes, paths, files = [], [], [], []
+        for i in range(len(ds)):
+            ref = refer.loadRefs(ds.ref_ids[i])[0]
+            ann = refer.Anns[ref["ann_id"]]
+            bbox = np.array(ann["bbox"], dtype=int)
+            bbox[2], bbox[3] = bbox[0] + bbox[2], bbox[1] + bbox[3]
+            image = refer.Imgs[ref["image_id"]]
+            h, w = int(image["height"]), int(image["width"])
+            arena.add_ref(ann["segmentation"], h, w, f"ref {ref['ref_id']} (annotation {ref['ann_id']})")
+            fname = recs[i][2]["file_name"]
+            boxes.append(bbox)
+            sizes.append((h, w))
+            paths.append(int(fname.split(".")[0].split("_")[-1]))
+            files.append(fname)
+        built = arena.build(self.device)
+        if self.targets is not None:
+            for i, ((lo, hi), (h, w)) in enumerate(zip(built.ranges.tolist(), sizes)):
+                ops.rle_target_nearest(built, lo, hi, h, w, S, out=self.targets[i])
+        else:
+            self.arena, self.sizes_host = built, sizes
+        return boxes, sizes, paths, files
+
     def _index_tokens(self, n):
         # token rows of every sentence, ref-major
         ds, dev = self.dataset, self.device
@@ -147,6 +186,8 @@ class HbmReferCache:
             t += self.targets.numel()
         if self.pseudo is not None:
             t += self.pseudo.numel()
+        if self.arena is not None:    # (cfg.poly_targets: run ends instead of masks)
+            t += self.arena.nbytes()
         return t + sum(m.numel() for m in self.eval_targets)
 
 
@@ -226,7 +267,11 @@ class HbmLoader:
             "word_ids": c.tokens[lo:hi].t().unsqueeze(0).unsqueeze(0),        # [1, 1, L, S_ref]
             "word_masks": c.token_masks[lo:hi].t().unsqueeze(0).unsqueeze(0),
         }
-        m = c.eval_targets[index]
+        if c.arena is not None:       # cfg.poly_targets: the ref's mask from its run ends (pixels covered by exactly one polygon)
+            a = c.arena
+            m = ops.rle_decode_sum_arena(a.ends, a.seg_off, a.ranges[index:index + 1], *c.sizes_host[index])[0] == 1
+        else:
+            m = c.eval_targets[index]
         targets = {
             "target": m.view(1, 1, *m.shape).to(torch.int64),
             "img_path": c.img_path[index].view(1),

@@ -3389,6 +3389,67 @@ def rle_decode_sum(sentences, H, W, names=None, device="cuda"):
     return rle_decode_sum_arena(ends, seg_off, rng, H, W)
 
 
+# ------------------------------------------------------------------------------------ REFER polygon targets (csrc/polymask.hip)
+def poly_runs(verts, poly_off, hw, host=None):
+    """cocomask.frPyObjects of P polygons on the device (dataset/poly_arena.py: PolyArena.build): verts int32 [V,2] upsampled
+    vertices, poly_off int64 [P+1], hw int32 [P,2] -> (ends int32 [runs + 1], seg_off int64 [P+1]), the arena rle_decode_sum_arena
+    reads.  Count, scan (torch.cumsum), emit: two launches for the whole split.  host = (index int64 [N], lens int64 [N], values
+    int32 [sum lens]): segments without vertices whose run ends the host supplies; they take slices of those lengths.  The arena's
+    builder has checked coordinates and sizes; nothing here reads them back but the total number of runs."""
+    for t, dt in ((verts, torch.int32), (poly_off, torch.int64), (hw, torch.int32)):
+        if not t.is_cuda:
+            raise NoGpuError("tris_amd ops run on MI355X only (got a CPU tensor); there is no CPU fallback")
+        if t.dtype != dt:
+            raise TypeError(f"expected {dt}, got {t.dtype}")
+    P_ = poly_off.numel() - 1
+    if P_ < 0 or hw.numel() != 2 * P_ or verts.dim() != 2 or verts.shape[1] != 2:
+        raise ValueError(f"poly_runs: verts {tuple(verts.shape)}, poly_off {tuple(poly_off.shape)}, hw {tuple(hw.shape)}")
+    verts, poly_off, hw = verts.contiguous(), poly_off.contiguous(), hw.contiguous()
+    dev = poly_off.device
+    n_runs = torch.empty(P_, dtype=torch.int32, device=dev)
+    if P_:
+        call("tris_poly_count_runs", P(verts), P(poly_off), P(hw), P_, P(n_runs), _stream())
+    if host is not None:
+        index, lens, values = host
+        n_runs[index] = lens.to(torch.int32)
+    seg_off = torch.zeros(P_ + 1, dtype=torch.int64, device=dev)
+    seg_off[1:] = torch.cumsum(n_runs, 0, dtype=torch.int64)
+    total = int(seg_off[-1])
+    ends = torch.zeros(total + 1, dtype=torch.int32, device=dev)      # (one spare word, as RleArena.to)
+    if P_:
+        call("tris_poly_emit_runs", P(verts), P(poly_off), P(hw), P(seg_off), P_, P(ends), _stream())
+    if host is not None and values.numel():
+        first = torch.cumsum(lens, 0) - lens
+        pos = torch.arange(values.numel(), device=dev) + torch.repeat_interleave(seg_off[index] - first, lens)
+        ends[pos] = values
+    return ends, seg_off
+
+
+def rle_target_nearest(arena, lo, hi, H, W, S, out=None):
+    """training target of one ref (ReferDataset.load_mask + transform.py:32): arena = (ends, seg_off) on the device or an object
+    with those attributes, segments lo .. hi-1 on an H x W canvas -> uint8 [S,S] = Pillow NEAREST resize of (decoded sum == 1);
+    the full-size mask is never formed"""
+    ends, seg_off = (arena.ends, arena.seg_off) if hasattr(arena, "ends") else arena
+    for t, dt in ((ends, torch.int32), (seg_off, torch.int64)):
+        if not t.is_cuda:
+            raise NoGpuError("tris_amd ops run on MI355X only (got a CPU tensor); there is no CPU fallback")
+        if t.dtype != dt:
+            raise TypeError(f"expected {dt}, got {t.dtype}")
+    if H < 1 or W < 1 or H * W > (1 << 24) or S < 1:
+        raise ValueError(f"rle_target_nearest: {H}x{W} -> {S}x{S} is empty or beyond 2^24 pixels")
+    if not 0 <= lo <= hi <= seg_off.numel() - 1 or hi - lo > 255:
+        raise ValueError(f"rle_target_nearest: segments {lo}..{hi} of {seg_off.numel() - 1} (at most 255 per ref)")
+    if out is None:
+        out = torch.empty(S, S, dtype=torch.uint8, device=ends.device)
+    else:
+        _chk_u8(out)
+        assert tuple(out.shape) == (S, S) and out.is_contiguous()
+    yi, = _pil_tables("nearest", H, S, ends.device)
+    xi, = _pil_tables("nearest", W, S, ends.device)
+    call("tris_rle_target_nearest_u8", P(ends), P(seg_off), lo, hi, H, W, P(yi), P(xi), S, S, P(out), _stream())
+    return out
+
+
 def eval_post_group(maps, targets_u8, signed=False, cams=True):
     """validate_referit.py:160-171 for the K sentences of one image in one call: maps [K,S,S] (or [K,1,S,S]), targets_u8 [K,oH,oW]
     counts -> (records int64 [K,4] on the device = I, U, first arg-max of cam, target count at the arg-max; cams [K,oH,oW], None
