@@ -446,29 +446,35 @@ int tris_xattn_px_fwd_f32(const float* Qv, const float* Kv, const float* Vv, con
 int tris_softmax_col_bwd_f32(const float* dY, const float* Y, float* dX, int B, int P, int N, float scale,
                              void* stream);
 /* training cls head on score [B,P,N]: bg channel + channel softmax + mean/max pooling + focal term
- * (model_stage1.py:80-108, focal_loss :122-123).  cls_fg may be NULL. */
+ * (model_stage1.py:80-108, focal_loss :122-123).  cls_fg may be NULL.  B, P, N >= 1; with cls_fg (the mean probability of
+ * sentence i in image i) N >= B.  One workgroup per image holds its logits in LDS: (P*(N+1) + 2P) floats forward,
+ * (P*(N+1) + 3P + 3N) backward, at most 150 KB.  Anything else returns hipErrorInvalidValue before a launch. */
 int tris_cls_head_fwd_f32(const float* score, float* cls_out, float* cls_fg, int B, int P, int N, float focal_p,
                           float focal_c, void* stream);
 int tris_cls_head_bwd_f32(const float* score, const float* g_cls_out, float* dscore, int B, int P, int N, float focal_p,
                           float focal_c, void* stream);
 /* diagonal response maps score[i,:,i] -> bilinear (align_corners=False) to SxS -> relu / sigmoid
- * (model_stage1.py:110-119, model/utils.py:5-10).  sig_map may be NULL (eval).  bwd ACCUMULATES into dscore. */
+ * (model_stage1.py:110-119, model/utils.py:5-10).  sig_map may be NULL (eval).  bwd ACCUMULATES into dscore.
+ * B, h, w, S >= 1, h*w <= 1024 and N >= B (image i reads column i), else hipErrorInvalidValue. */
 int tris_maps_fwd_f32(const float* score, float* relu_map, float* sig_map, int B, int h, int w, int N, int S,
                       void* stream);
 int tris_maps_bwd_f32(const float* score, const float* d_relu, const float* d_sig, float* dscore, int B, int h, int w,
                       int N, int S, void* stream);
-/* F.interpolate(mode='bilinear') on [planes, Hi, Wi] (train_stage1.py:328-329, validate.py:180) */
+/* F.interpolate(mode='bilinear') on [planes, Hi, Wi] (train_stage1.py:328-329, validate.py:180).  Up- and down-scale, both
+ * align_corners conventions; planes and all four sizes >= 1, else hipErrorInvalidValue. */
 int tris_resize_bilinear_fwd_f32(const float* X, float* Y, int planes, int Hi, int Wi, int Ho, int Wo,
                                  int align_corners, void* stream);
 int tris_resize_bilinear_bwd_f32(const float* dY, float* dX, int planes, int Hi, int Wi, int Ho, int Wo,
                                  int align_corners, void* stream);
 /* fg = cam * img written directly as the aux ViT's patch-GEMM operand [B, (R/ps)^2, C*ps*ps]
- * (train_stage1.py:333-338 + CLIP/clip/model.py:405,420-422) */
+ * (train_stage1.py:333-338 + CLIP/clip/model.py:405,420-422).  cam [B,1,R,R], img [B,C,R,R]: square images of whole patches,
+ * B, C, R, ps >= 1 and R % ps == 0, else hipErrorInvalidValue. */
 int tris_fg_patch_fwd_f32(const float* cam, const float* img, float* patches, int B, int C, int R, int ps,
                           void* stream);
 int tris_fg_patch_bwd_f32(const float* dpatches, const float* img, float* dcam, int B, int C, int R, int ps,
                           void* stream);
-/* class token + positional embedding (CLIP/clip/model.py:423-424) */
+/* class token + positional embedding (CLIP/clip/model.py:423-424): emb [B,T-1,W] -> x [B,T,W].  B, W >= 1 and T >= 2 (the
+ * class token and at least one patch), else hipErrorInvalidValue. */
 int tris_vit_assemble_fwd_f32(const float* emb, const float* cls, const float* pos, float* x, int B, int T, int W,
                               void* stream);
 int tris_vit_assemble_bwd_f32(const float* dx, float* demb, int B, int T, int W, void* stream);

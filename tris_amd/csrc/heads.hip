@@ -477,7 +477,8 @@ extern "C" int tris_softmax_bwd_f32(const float* dY, const float* Y, float* dX, 
 }
 extern "C" int tris_cls_head_fwd_f32(const float* score, float* cls_out, float* cls_fg, int B, int P, int N,
                                      float focal_p, float focal_c, void* stream) {
-  size_t lds = (size_t)(P * (N + 1) + 2 * P) * sizeof(float);
+  if (B < 1 || P < 1 || N < 1 || (cls_fg != nullptr && N < B)) return (int)hipErrorInvalidValue;  // cls_fg[i] is sentence i of image i
+  size_t lds = ((size_t)P * (N + 1) + 2 * (size_t)P) * sizeof(float);
   if (lds > 150 * 1024) return (int)hipErrorInvalidValue;
   static bool big_ok = false;  // more than the default 64 KB of dynamic LDS (a 20 x 20 ViT grid with 48 sentences: 82 KB)
   if (lds > 60000 && !big_ok) {
@@ -492,7 +493,8 @@ extern "C" int tris_cls_head_fwd_f32(const float* score, float* cls_out, float* 
 }
 extern "C" int tris_cls_head_bwd_f32(const float* score, const float* g, float* dscore, int B, int P, int N,
                                      float focal_p, float focal_c, void* stream) {
-  size_t lds = (size_t)(P * (N + 1) + 3 * P + 3 * N) * sizeof(float);
+  if (B < 1 || P < 1 || N < 1) return (int)hipErrorInvalidValue;
+  size_t lds = ((size_t)P * (N + 1) + 3 * (size_t)P + 3 * (size_t)N) * sizeof(float);
   if (lds > 150 * 1024) return (int)hipErrorInvalidValue;
   static bool big_ok = false;
   if (lds > 60000 && !big_ok) {
@@ -507,7 +509,8 @@ extern "C" int tris_cls_head_bwd_f32(const float* score, const float* g, float* 
 }
 extern "C" int tris_maps_fwd_f32(const float* score, float* relu_map, float* sig_map, int B, int h, int w, int N, int S,
                                  void* stream) {
-  if (h * w > 1024) return (int)hipErrorInvalidValue;
+  if (B < 1 || h < 1 || w < 1 || S < 1 || N < B) return (int)hipErrorInvalidValue;  // the diagonal score[i][.][i] needs N >= B
+  if ((long)h * w > 1024) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(maps_fwd_kernel, dim3(cdiv((long)S * S, 256), B), dim3(256), 0, (hipStream_t)stream, score,
                      relu_map, sig_map, h, w, N, S);
   TRIS_LAUNCH_CHECK();
@@ -515,7 +518,8 @@ extern "C" int tris_maps_fwd_f32(const float* score, float* relu_map, float* sig
 }
 extern "C" int tris_maps_bwd_f32(const float* score, const float* d_relu, const float* d_sig, float* dscore, int B,
                                  int h, int w, int N, int S, void* stream) {
-  if (h * w > 1024) return (int)hipErrorInvalidValue;
+  if (B < 1 || h < 1 || w < 1 || S < 1 || N < B) return (int)hipErrorInvalidValue;
+  if ((long)h * w > 1024) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(maps_bwd_kernel, dim3(h * w, B), dim3(256), 0, (hipStream_t)stream, score, d_relu, d_sig, dscore, h,
                      w, N, S);
   TRIS_LAUNCH_CHECK();
@@ -523,6 +527,7 @@ extern "C" int tris_maps_bwd_f32(const float* score, const float* d_relu, const 
 }
 extern "C" int tris_resize_bilinear_fwd_f32(const float* X, float* Y, int planes, int Hi, int Wi, int Ho, int Wo,
                                             int align_corners, void* stream) {
+  if (planes < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(resize_fwd_kernel, dim3(grid_for((long)planes * Ho * Wo)), dim3(256), 0, (hipStream_t)stream, X, Y,
                      planes, Hi, Wi, Ho, Wo, align_corners);
   TRIS_LAUNCH_CHECK();
@@ -530,6 +535,7 @@ extern "C" int tris_resize_bilinear_fwd_f32(const float* X, float* Y, int planes
 }
 extern "C" int tris_resize_bilinear_bwd_f32(const float* dY, float* dX, int planes, int Hi, int Wi, int Ho, int Wo,
                                             int align_corners, void* stream) {
+  if (planes < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(resize_bwd_kernel, dim3(cdiv((long)planes * Hi * Wi, 256)), dim3(256), 0, (hipStream_t)stream, dY,
                      dX, planes, Hi, Wi, Ho, Wo, align_corners);
   TRIS_LAUNCH_CHECK();
@@ -537,6 +543,7 @@ extern "C" int tris_resize_bilinear_bwd_f32(const float* dY, float* dX, int plan
 }
 extern "C" int tris_fg_patch_fwd_f32(const float* cam, const float* img, float* patches, int B, int C, int R, int ps,
                                      void* stream) {
+  if (B < 1 || C < 1 || R < 1 || ps < 1 || R % ps != 0) return (int)hipErrorInvalidValue;  // whole patches only
   hipLaunchKernelGGL(fg_patch_fwd_kernel, dim3(grid_for((long)B * C * R * R)), dim3(256), 0, (hipStream_t)stream, cam,
                      img, patches, B, C, R, ps);
   TRIS_LAUNCH_CHECK();
@@ -544,6 +551,7 @@ extern "C" int tris_fg_patch_fwd_f32(const float* cam, const float* img, float* 
 }
 extern "C" int tris_fg_patch_bwd_f32(const float* dpatches, const float* img, float* dcam, int B, int C, int R, int ps,
                                      void* stream) {
+  if (B < 1 || C < 1 || R < 1 || ps < 1 || R % ps != 0) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(fg_patch_bwd_kernel, dim3(cdiv((long)B * R * R, 256)), dim3(256), 0, (hipStream_t)stream, dpatches,
                      img, dcam, B, C, R, ps);
   TRIS_LAUNCH_CHECK();
@@ -551,12 +559,14 @@ extern "C" int tris_fg_patch_bwd_f32(const float* dpatches, const float* img, fl
 }
 extern "C" int tris_vit_assemble_fwd_f32(const float* emb, const float* cls, const float* pos, float* x, int B, int T,
                                          int W, void* stream) {
+  if (B < 1 || T < 2 || W < 1) return (int)hipErrorInvalidValue;  // the class token and at least one patch
   hipLaunchKernelGGL(vit_assemble_kernel, dim3(cdiv((long)B * T * W, 256)), dim3(256), 0, (hipStream_t)stream, emb, cls,
                      pos, x, B, T, W);
   TRIS_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int tris_vit_assemble_bwd_f32(const float* dx, float* demb, int B, int T, int W, void* stream) {
+  if (B < 1 || T < 2 || W < 1) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(vit_assemble_bwd_kernel, dim3(cdiv((long)B * (T - 1) * W, 256)), dim3(256), 0, (hipStream_t)stream,
                      dx, demb, B, T, W);
   TRIS_LAUNCH_CHECK();

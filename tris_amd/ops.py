@@ -2734,6 +2734,8 @@ class ScoreHeadsFn(torch.autograd.Function):
 
 
 def score_heads(score, h, w, S, train, focal_p=3.0, focal_c=0.01):
+    if score.dim() != 3 or h * w != score.shape[1]:
+        raise ValueError(f"score_heads: score {tuple(score.shape)} is not [B, h * w, N] with h * w = {h} * {w}")
     return ScoreHeadsFn.apply(score, h, w, S, train, focal_p, focal_c)
 
 
@@ -2787,6 +2789,12 @@ class FgPatchFn(torch.autograd.Function):
 
 
 def fg_patches(cam, img, ps):
+    if img.dim() != 4 or img.shape[2] != img.shape[3]:
+        raise ValueError(f"fg_patches: img {tuple(img.shape)} is not a batch of square images [B,C,R,R]")
+    if tuple(cam.shape) != (img.shape[0], 1, img.shape[2], img.shape[3]):
+        raise ValueError(f"fg_patches: cam {tuple(cam.shape)} is not {(img.shape[0], 1, img.shape[2], img.shape[3])}")
+    if ps < 1 or img.shape[2] % ps:
+        raise ValueError(f"fg_patches: patch size {ps} does not divide the image size {img.shape[2]}")
     return FgPatchFn.apply(cam, img, ps)
 
 
