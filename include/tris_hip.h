@@ -147,7 +147,9 @@ int tris_bn_apply_f32(const float* X, const float* mean, const float* invstd, co
  * without a residual input): the ReLU mask is recomputed from X with tris_bn_apply_f32's own expression -- same sign bit
  * for bit -- and Y is not read (one 4-byte stream less in each of the two passes).  reduce, dz_out != NULL: the masked
  * gradient dz is also written; tris_bn_bwd_apply_f32 may then be given dY = dz_out, Y = NULL, dZ = NULL (dz is already
- * the residual branch's gradient): 7 activation-sized streams over the two passes instead of 8. */
+ * the residual branch's gradient): 7 activation-sized streams over the two passes instead of 8.
+ * Every entry point of this family (stats, apply, reduce, bwd_apply and the pool forms) returns hipErrorInvalidValue and launches
+ * nothing when C % 4 != 0; the reduce also when exactly one of gamma_mask / beta_mask is given. */
 /* The reduce pass fused into the PRODUCER of dY where that is a 1x1-convolution / Linear data gradient (the next layer's
  * backward, CLIP/clip/model.py:42-55 read in reverse): dZ[M,N] = mask(dY[M,K] . Wt[K,N] (+ resid)) with the mask of the
  * BatchNorm(+ReLU) whose raw input is bn_x [M,N] -- from its output bn_y (residual form), or, bn_y == NULL, recomputed from

@@ -41,7 +41,10 @@ inline int big_grid(long n4) { return (int)((n4 + BIG_PIECE - 1) / BIG_PIECE); }
 
 // ------------------------------------------------------------------------------------------------------
 // Column (per-channel) partial reductions.  Block = 256 threads covering CVB = min(C/4,256) channel-vectors
-// x RS = 256/CVB rows at a time.  MODE 0: shifted sum / sum of squares of X (BN forward statistics).
+// x RS = 256/CVB rows at a time.  MODE 0: plain one-pass sum / sum of squares of X in fp64, no shift (BN forward statistics;
+// bn_finalize_kernel forms var = E[x^2] - mean^2 in fp64, so with U53 = 2^-53 the variance is within
+// 2^-23 var + (M + 4) U53 (var + mean^2) of the two-pass value: the cancellation costs a relative M U53 mean^2 / var, below one
+// float ulp as long as mean^2 / var < 2^29 / M -- tests/oracle_bn.py states the bound, tests/test_gpu_bn.py asserts it).
 // MODE 1: sum(dz), sum(dz * xhat) with dz = dY * (Y > 0 if Y given)  (BN backward).  MODE 2: plain column sum.
 // part layout: [nblocks][2][C].
 // ------------------------------------------------------------------------------------------------------
@@ -822,8 +825,8 @@ inline int grid_for(long n, int block = 256) {
   if (g < 1) g = 1;
   return (int)g;
 }
-// grid for the channel-invariant BN apply kernels: gridDim*256 must be a multiple of C/4 (C/4 = 2^k or any divisor-friendly
-// width); returns 0 when that cannot be arranged (caller reports an error: BN widths on this path are powers of two)
+// grid for the channel-invariant BN apply kernels: gridDim*256 must be a multiple of C/4, so the grid is rounded up to a multiple
+// of (C/4) / gcd(C/4, 256) -- any width with C % 4 == 0 (tests/test_gpu_bn.py runs 12, 48 and 1028 beside the powers of two)
 inline int bn_grid(long n4, int C) {
   const long cv = C / 4;
   long g = (n4 + 255) / 256;
@@ -1095,6 +1098,7 @@ extern "C" int tris_bn_bwd_apply_f32(const float* dY, const float* Y, const floa
                                      const float* invstd, const float* gamma, const float* sum_dz, const float* sum_dzx,
                                      float inv_count, float* dX, float* dZ, long M, int C, const float* beta_mask,
                                      void* stream) {
+  if (C % 4) return (int)hipErrorInvalidValue;
   long n4 = M * C / 4;
   const int streams = 3 + ((Y && !beta_mask) ? 1 : 0) + (dZ ? 1 : 0);
   if (big_form(n4, C, streams))
