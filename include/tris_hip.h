@@ -47,6 +47,15 @@ int tris_gemm_f32(const float* A, const float* B, float* C, int M, int N, int K,
  * when the fast kernel does not serve its operands. */
 int tris_gemm_epilogue_next(float* pre_out, const float* dact_x);
 
+/* One-shot: the NEXT tris_gemm_f32 or tris_gemm_bnbwd_f32 launched from the calling thread (batch 1) takes its residual POOLED: the M
+ * rows of C are the pixels of a [M / (H W), H, W] map and resid is [M / 4, ldr], the gradient of the 2x2 average pool of that map --
+ * the epilogue adds 0.25f * resid[pooled pixel of m], the value tris_avgpool2_bwd_f32 would have written to a full-size tensor for it
+ * to read back (the shortcut of a stride-2 Bottleneck, reference CLIP/clip/model.py:33-38; bit-identical to those two launches).
+ * H and W even, M a multiple of H W, resid 16-byte aligned with ldr % 4 == 0: otherwise the armed product FAILS
+ * (hipErrorInvalidValue).  It runs without split-K; where the fast kernel does not serve its operands tris_gemm_f32 returns
+ * TRIS_DECLINED and tris_gemm_bnbwd_f32 reports *part_rows = 0 -- nothing launched, arming consumed. */
+int tris_gemm_resid_pool_next(int H, int W);
+
 /* One-shot: the NEXT tris_gemm_f32 launched from the calling thread may finish a split-K product INSIDE its own launch: each tile's
  * k slices take a ticket from tickets[tile], and the block that arrives last sums the tile's slabs in the order of the reduce launch it replaces (the result is
  * the separate reduce launch's, bit for bit, whichever block that is), applies bias / activation / residual and writes C.  Used for
@@ -233,6 +242,15 @@ int tris_h2_next_planes(const unsigned* amaxA, const unsigned* amaxB, int flags)
 int tris_bn_apply_pl_f32(const float* X, const float* mean, const float* invstd, const float* gamma, const float* beta,
                          const float* resid, int resid_kind, const unsigned* resid_word, float* Ypl, const unsigned* out_word, long M,
                          int C, int relu, void* stream);
+/* The closing pass of a down-sampling Bottleneck (reference CLIP/clip/model.py:42-55, out = relu(bn3(conv3) + downsample(x))) with the
+ * shortcut's BatchNorm inside it: Ypl = relu(bn3(X3) + bn_s(Xs)), X3 and Xs [M, C] raw convolution outputs.  Bit-identical to
+ * tris_bn_apply_f32(Xs, .._s, no residual, no ReLU) followed by tris_bn_apply_pl_f32(X3, .._3, that tensor as resid_kind 1, relu) at
+ * the same *out_word -- the shortcut's fp32 output is never written or read back.  *out_word: an upper bound of the output, e.g. the sum
+ * of the two Samuelson bounds (tris_bn_finalize_bound_f32 for the shortcut, then for bn3 with the shortcut's word as add_word).  Takes a
+ * tris_bn_mask_next arming like tris_bn_apply_pl_f32.  Refused: C % 8, 2048 % C, a null or misaligned pointer. */
+int tris_bn_apply_pair_pl_f32(const float* X3, const float* mean3, const float* invstd3, const float* gamma3, const float* beta3,
+                              const float* Xs, const float* mean_s, const float* invstd_s, const float* gamma_s, const float* beta_s,
+                              float* Ypl, const unsigned* out_word, long M, int C, void* stream);
 int tris_bn_bwd_reduce_pl_f32(const float* dY, const float* Ypl, const float* X, const float* mean, const float* invstd, long M, int C,
                               float* sum_dz, float* sum_dzx, float* workspace, float* dz_out, void* stream);
 int tris_bn_apply_pool_pl_f32(const float* X, const float* mean, const float* invstd, const float* gamma, const float* beta,
@@ -241,6 +259,26 @@ int tris_avgpool2_fwd_pl_f32(const float* Xpl, float* Ypl, const unsigned* word,
 int tris_bn_bwd_apply_pl_f32(const float* dY, const float* Ypl, const float* X, const float* mean, const float* invstd,
                              const float* gamma, const float* sum_dz, const float* sum_dzx, float inv_count, float* dXpl,
                              const unsigned* out_word, float* dZ, long M, int C, const float* beta_mask, void* stream);
+/* The backward of the pair above, where bn3's sums come out of the consuming product's epilogue (tris_gemm_bnbwd_f32):
+ *   tris_gemm_bnbwd_x2_next arms the calling thread's NEXT tris_gemm_bnbwd_f32 with a SECOND BatchNorm that receives the same masked
+ *     gradient dZ (the shortcut's): raw input x2 [M, N] (layout of dZ), its mean and invstd; the launch also leaves sum(dz * xhat2) per
+ *     column in the first N doubles of each row of part2 [*part_rows][2][N] (the row layout of `part`), summed like the other two
+ *     sums; dZ and `part` are the bits of the call without the arming.  Taken first thing; all pointers non-null and 16-byte aligned.
+ *   tris_part_finalize_pair_f32: tris_part_finalize_bound_f32 for both BatchNorms in ONE launch -- sum_dz, sum_dzx from `part`,
+ *     sum_dzx2 from part2, sum_dz a second time to sum_dz_b (the second BatchNorm's dbeta), and the bound words of the two dx (the
+ *     expression of tris_bn_bwd_bound_f32 with the same *dz_word).
+ *   tris_bn_bwd_apply_pair_pl_f32: dX3pl, dXspl (planes at *word3 / *word_s) from ONE read of dZ, X3 and Xs; for each of the two the
+ *     arithmetic of tris_bn_bwd_apply_pl_f32 without a mask (dZ arrives masked) -- given the same sums, the same bits as two such
+ *     launches.  Refused: C % 8, 2048 % C, a null or misaligned pointer, one word or one output for both. */
+int tris_gemm_bnbwd_x2_next(const float* x2, const float* mean2, const float* invstd2, double* part2);
+int tris_part_finalize_pair_f32(const double* part, const double* part2, int rows, int C, float* sum_dz, float* sum_dzx, float* sum_dz_b,
+                                float* sum_dzx2, const float* gamma, const float* invstd, const float* gamma2, const float* invstd2,
+                                float inv_count, float xhat_max, const unsigned* dz_word, unsigned* bound_out, unsigned* bound_out2,
+                                void* stream);
+int tris_bn_bwd_apply_pair_pl_f32(const float* dZ, const float* X3, const float* mean3, const float* invstd3, const float* gamma3,
+                                  const float* sum_dzx3, const float* Xs, const float* mean_s, const float* invstd_s,
+                                  const float* gamma_s, const float* sum_dzx_s, const float* sum_dz, float inv_count, float* dX3pl,
+                                  const unsigned* word3, float* dXspl, const unsigned* word_s, long M, int C, void* stream);
 int tris_bn_bwd_apply_pool_pl_f32(const float* dYp, const float* X, const float* mean, const float* invstd, const float* gamma,
                                   const float* beta, const float* sum_dz, const float* sum_dzx, float inv_count, float* dXpl,
                                   const unsigned* out_word, int B, int H, int W, int C, void* stream);

@@ -68,16 +68,20 @@ class BatchNorm2d(nn.Module):
             self.num_batches_tracked += self._nbt_pending
             self._nbt_pending = 0
 
-    def forward(self, x, resid=None, relu=False, grad_box=None, lazy=False, bwd_link=False, pool=False, planes=False, dx_planes=False):
+    def forward(self, x, resid=None, relu=False, grad_box=None, lazy=False, bwd_link=False, pool=False, planes=False, dx_planes=False,
+                pair=False):
         """pool=True: returns avgpool2(relu(bn(x))) -- the AvgPool2d(2) that follows is part of the op (train mode: one kernel,
         the full-size activation is never written).
         bwd_link=True: the caller guarantees that the output has exactly ONE autograd consumer; if that is a 1x1 convolution
-        its data gradient does this BatchNorm's backward reduction in its epilogue (ops._BnBwdLink)"""
+        its data gradient does this BatchNorm's backward reduction in its epilogue (ops._BnBwdLink)
+        pair=True: the output is read by ONE BatchNorm, as its residual, and by nothing else (a Bottleneck's shortcut): that pass may
+        normalise this input itself, the output is then never written (ops.BatchNormFn, cfg.bn_pair)"""
         if self.training:
             self._nbt_pending += 1
         group = self.process_group if self.training else None
         return ops.batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, resid, relu,
-                              self.training, self.momentum, self.eps, group, grad_box, lazy, bwd_link, pool, planes, dx_planes)
+                              self.training, self.momentum, self.eps, group, grad_box, lazy, bwd_link, pool, planes, dx_planes,
+                              **({"pair": True} if pair else {}))
 
 
 class AvgPool2d(nn.Module):
@@ -139,7 +143,9 @@ class Bottleneck(nn.Module):
                 idn = self.downsample[1](self.downsample[0](x, grad_box_out=box), stats=tr)
             else:
                 idn = self.downsample[1](self.downsample[0](x), stats=tr, grad_box_out=box)
-            idn = self.downsample[2](idn, dx_planes=pl)     # (the shortcut's output stays fp32: bn3's pass is its only reader)
+            # (bn3's pass is the shortcut's only reader: on operand planes it normalises the shortcut's raw convolution output itself --
+            #  relu(bn3(x3) + bn_s(xs)) in one launch, cfg.bn_pair -- otherwise the shortcut's output is written, as fp32)
+            idn = self.downsample[2](idn, dx_planes=pl, pair=pl)
             return self.bn3(out, resid=idn, relu=True, bwd_link=link_out, planes=pl, dx_planes=pl)
         return self.bn3(out, resid=x, relu=True, grad_box=box, bwd_link=link_out, planes=pl, dx_planes=pl)  # relu(bn3(conv3) + identity), fused
 

@@ -51,6 +51,12 @@ assigning to it (`cfg.step_graph = "seg"`, `monkeypatch.setattr(cfg, "bn_pool", 
                                                BatchNorm-backward epilogue reads that instead of the plane element
   step_graph_rerecord TRIS_STEP_GRAPH_RERECORD replayed step: a batch shape other than the recorded one, seen this many steps IN A ROW, is recorded in its place
                                                (default 3: a recording made on a ragged first batch does not leave the run eager; 0: never)
+  bn_pair            TRIS_BN_PAIR              operand planes, training, no SyncBatchNorm group: a down-sampling Bottleneck's closing pass normalises the shortcut as well
+                                               (relu(bn3(x3) + bn_s(xs)) in one launch, the shortcut BatchNorm's fp32 output never written); 0: the two launches
+  bn_pair_parts      TRIS_BN_PAIR_PARTS        which parts of bn_pair are on, comma-separated: "fwd" the forward pair pass, "pool" the stride-2 shortcut's pooled gradient
+                                               read in place by conv1's data-gradient epilogue, "bwd" the backward pair (third sum in the consuming product's epilogue,
+                                               one finalizer, one apply pass; needs "fwd").  Default "fwd,pool": the backward pair is built and tested but its gain as a
+                                               part (0.20 ms) stayed under three spreads of the runs without it (profiles/bn_pair_ab.txt, session 4)
   side_param_grads   TRIS_SIDE_PARAM_GRADS     bias / InstanceNorm-parameter gradients (column sums nothing in the backward waits for) on the weight-gradient stream
   fuse_splitk        TRIS_FUSE_SPLITK_PY       split-K products armed with a ticket array: the last block of a tile sums the slabs in the product's own launch (default 0: measured slower)
 """
@@ -109,6 +115,8 @@ class _Config:
         self.aux_text_early = _flag("TRIS_AUX_TEXT_EARLY", True)
         self.text_pack = _flag("TRIS_TEXT_PACK", True)
         self.bn_bitmask = _flag("TRIS_BN_BITMASK", True)
+        self.bn_pair = _flag("TRIS_BN_PAIR", True)
+        self.bn_pair_parts = e("TRIS_BN_PAIR_PARTS", "fwd,pool")
         self.gemm_convert = int(e("TRIS_GEMM_CONVERT", "0"))
         self.step_graph_rerecord = int(e("TRIS_STEP_GRAPH_RERECORD", "3"))
         self.side_param_grads = _flag("TRIS_SIDE_PARAM_GRADS", True)

@@ -47,7 +47,7 @@ namespace {
 // travel with the nontemporal policy -- norm.hip "BIG form" has the measurement; split-K slabs are re-read at once and stay cached.
 static int stream_nt(const GemmParams& p, int batch) {
   if (!tris_internal_stream_form) return 0;
-  const long streams = 1 + (p.resid ? 1 : 0) + (p.bnb_x ? 1 : 0) + (p.bnb_y ? 1 : 0);
+  const long streams = 1 + ((p.resid && !p.resid_pool_h) ? 1 : 0) + (p.bnb_x ? 1 : 0) + (p.bnb_y ? 1 : 0) + (p.bnb_x2 ? 1 : 0);   // (a pooled residual is re-read: cached)
   return (long)p.M * p.N * 4 * batch * streams > ((long)tris_internal_stream_form << 20) ? 1 : 0;
 }
 
@@ -262,7 +262,10 @@ int launch_cfg(GemmParams& p, int batch, float* ws, long ws_bytes, hipStream_t s
   Cfg h = heuristic_cfg(p, batch, ws, ws_bytes);
   if (!autotune_enabled() || g_opt.force_tile) return run_cfg<AK, BKIND>(p, batch, ws, st, h);
   const bool stat = p.stat_part != nullptr;  // fused BN statistics: 128-row tiles and no split-K are fixed, the tile width is tuned
-  const TuneKey key = {AK, BKIND + (stat ? 16 : 0) + (p.bnb_x != nullptr ? 32 : 0), p.M, p.N, p.K, batch, g_gemm_mode};
+  // (EPI_PAIR products -- pooled residual, third sum -- run kernels of their own and never split K: a key of their own, so that they
+  //  neither inherit a configuration timed on the EPI_STD kernels nor hand theirs to a plain product of the same shape)
+  const bool pairx = p.resid_pool_h != 0 || p.bnb_x2 != nullptr;
+  const TuneKey key = {AK, BKIND + (stat ? 16 : 0) + (p.bnb_x != nullptr ? 32 : 0) + (pairx ? 64 : 0), p.M, p.N, p.K, batch, g_gemm_mode};
   {
     std::lock_guard<std::mutex> lk(g_tune_mu);
     auto it = g_tuned.find(key);
@@ -502,6 +505,34 @@ extern "C" int tris_gemm_epilogue_next(float* pre_out, const float* dact_x) {
   return 0;
 }
 
+// One-shot arming of the NEXT tris_gemm_f32 / tris_gemm_bnbwd_f32 of the calling thread: its residual is the gradient of a 2x2 average
+// pool over the [.., H, W] pixel map its rows stand for (GemmParams::resid_pool_h / _w).  Both entry points take the arming first thing.
+struct ResidPoolNext { int h, w; };
+static thread_local ResidPoolNext g_resid_pool_next = {0, 0};
+extern "C" int tris_gemm_resid_pool_next(int H, int W) {
+  g_resid_pool_next = {H, W};
+  return 0;
+}
+static ResidPoolNext resid_pool_take() {
+  const ResidPoolNext r = g_resid_pool_next;
+  g_resid_pool_next = {0, 0};
+  return r;
+}
+// the geometry the epilogue can index: whole images of even height and width, a residual with 16-byte rows
+static bool resid_pool_ok(const ResidPoolNext& r, int M, int N, const float* resid, long ldr) {
+  return r.h > 0 && r.w > 0 && !(r.h & 1) && !(r.w & 1) && (long)M % ((long)r.h * r.w) == 0 && resid != nullptr && al16(resid) &&
+         ldr >= N && ldr % 4 == 0;
+}
+
+// One-shot arming of the NEXT tris_gemm_bnbwd_f32 of the calling thread with a second BatchNorm that receives the same masked
+// gradient (GemmParams::bnb_x2 ...): the launch also leaves sum(dz * xhat2) per column in part2
+struct Bnb2Next { const float *x2, *mean2, *invstd2; double* part2; bool armed; };
+static thread_local Bnb2Next g_bnb2_next = {nullptr, nullptr, nullptr, nullptr, false};
+extern "C" int tris_gemm_bnbwd_x2_next(const float* x2, const float* mean2, const float* invstd2, double* part2) {
+  g_bnb2_next = {x2, mean2, invstd2, part2, true};
+  return 0;
+}
+
 // One-shot arming of the NEXT tris_gemm_f32 of the calling thread with a ticket array for the fused split-K finish (gemm_fast.h):
 // `count` ints, ZERO when handed over and left zero by every launch; private to the stream the product is launched on (two
 // products in flight at once must not share one).  Without it a split-K product sums its slabs in a second launch, as before.
@@ -523,8 +554,10 @@ extern "C" int tris_gemm_f32(const float* A, const float* B, float* C, int M, in
   g_epi_next.armed = false;
   const TicketsNext tkn = g_tickets_next;
   g_tickets_next = {nullptr, 0};
+  const ResidPoolNext rpool = resid_pool_take();
+  const bool pooled = rpool.h != 0 || rpool.w != 0;
   if (M <= 0 || N <= 0 || batch <= 0) return 0;
-  if (K <= 0) return (int)hipErrorInvalidValue;
+  if (K <= 0 || (pooled && !resid_pool_ok(rpool, M, N, resid, ldr))) return (int)hipErrorInvalidValue;
   GemmParams p = {};
   p.amax_out = amax_out;
   p.tickets = tkn.t;
@@ -548,6 +581,12 @@ extern "C" int tris_gemm_f32(const float* A, const float* B, float* C, int M, in
   hipStream_t st = (hipStream_t)stream;
   if (epi.armed) {   // the extras live in the fast kernel's one-pass epilogue only: no split-K, no generic kernel
     if (batch != 1 || transA || !gemm_fast_ok(p)) return TRIS_DECLINED;
+    workspace = nullptr;
+    ws_bytes = 0;
+  }
+  if (pooled) {      // ... and so does the pooled residual
+    if (batch != 1 || transA || !gemm_fast_ok(p) || epi.armed) return TRIS_DECLINED;
+    p.resid_pool_h = rpool.h; p.resid_pool_w = rpool.w;
     workspace = nullptr;
     ws_bytes = 0;
   }
@@ -858,14 +897,23 @@ extern "C" int tris_gemm_bnbwd_f32(const float* dY, const float* Wt, float* dZ, 
                                    const float* gamma, const float* beta, double* part, int* part_rows, void* stream) {
   const H2Next h2n = h2_take();
   unsigned* amax_out = tris_internal_take_amax_next();   // (one-shot by-product: the amax word of the masked gradient dZ)
+  const ResidPoolNext rpool = resid_pool_take();
+  const bool pooled = rpool.h != 0 || rpool.w != 0;
+  const Bnb2Next b2 = g_bnb2_next;
+  g_bnb2_next.armed = false;
   *part_rows = 0;
   if (M <= 0 || N <= 0 || K <= 0 || bn_x == nullptr || part == nullptr) return (int)hipErrorInvalidValue;
+  if (b2.armed && (b2.x2 == nullptr || b2.mean2 == nullptr || b2.invstd2 == nullptr || b2.part2 == nullptr || !al16(b2.x2) ||
+                   !al16(b2.mean2) || !al16(b2.invstd2) || !al16(b2.part2)))
+    return (int)hipErrorInvalidValue;
+  if (pooled && !resid_pool_ok(rpool, M, N, resid, ldr)) return (int)hipErrorInvalidValue;
   if (bn_y == nullptr && (gamma == nullptr || beta == nullptr)) return (int)hipErrorInvalidValue;
   GemmParams p = {};
   p.amax_out = amax_out;
   p.A = dY; p.B = Wt; p.C = dZ; p.M = M; p.N = N; p.K = K;
   p.lda = K; p.ldb = N; p.ldc = N; p.alpha = 1.f;
   p.resid = resid; p.ldr = ldr;
+  if (pooled) { p.resid_pool_h = rpool.h; p.resid_pool_w = rpool.w; }
   p.vecA = al16(dY) && (K % 4 == 0);
   p.vecB = al16(Wt) && (N % 4 == 0);
   p.fastA = p.vecA;
@@ -875,6 +923,7 @@ extern "C" int tris_gemm_bnbwd_f32(const float* dY, const float* Wt, float* dZ, 
   if (!stats_eligible(p) || !al || N % 4 != 0) return 0;
   p.stat_part = part;
   p.bnb_x = bn_x; p.bnb_y = bn_y; p.bnb_mean = mean; p.bnb_invstd = invstd; p.bnb_gamma = gamma; p.bnb_beta = beta;
+  if (b2.armed) { p.bnb_x2 = b2.x2; p.bnb_mean2 = b2.mean2; p.bnb_invstd2 = b2.invstd2; p.stat_part2 = b2.part2; }
   *part_rows = cdiv(M, 128);
   H2Guard h2(p, h2n);
   if (h2.bad) return (int)hipErrorInvalidValue;

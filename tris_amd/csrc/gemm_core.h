@@ -462,6 +462,9 @@ int run_cfg(GemmParams p, int batch, float* ws, hipStream_t st, Cfg cfg, int mod
   const bool fast = gemm_fast_ok(p);
   if (bn == 32 && !fast) bm = bn = 64;  // the 128x32 tile exists in the fast kernel only
   const bool xtra = p.pre_out != nullptr || p.dact_x != nullptr;   // (tris_gemm_epilogue_next: classic loop, one slice, fast kernel)
+  const bool pairx = p.resid_pool_h != 0 || p.bnb_x2 != nullptr;   // (EPI_PAIR: one slice, fast kernel, row-major A; any loop form)
+  if (pairx) splitk = 1;   // (one pass over C: whatever configuration arrives, the slices are one)
+  if (pairx && (!fast || xtra || !(AK == A_ROWK && (BKIND == B_NK || BKIND == B_KN)))) return (int)hipErrorInvalidValue;
   if (mode == 4 && !fast) return (int)hipErrorInvalidValue;   // (operand planes exist for the fast kernel only: the caller checks)
   const bool pipe = cfg.pipe == 1 && (mode == 1 || mode == 3 || mode == 4) && fast && bn != 32 && !xtra;   // (the pipelined loop: x3 and h2)
   // cfg.pipe 2 | 3: the LDS-DMA loop of gemm_fast.h (operand planes, row-major A x B^T): 2 = eight waves per 128 x 128 tile (2 x 4),
@@ -510,6 +513,7 @@ int run_cfg(GemmParams p, int batch, float* ws, hipStream_t st, Cfg cfg, int mod
   else
     p.vecC = (p.N % 4 == 0) && al16(p.C) && (p.ldc % 4 == 0) && (p.sC % 4 == 0) &&
              (!p.resid || (al16(p.resid) && p.ldr % 4 == 0 && p.sR % 4 == 0)) && (p.bias_mode != 1 || al16(p.bias));
+  if (p.bnb_x2 != nullptr && (bm != 128 || !p.vecC)) return (int)hipErrorInvalidValue;   // (the third sum: vector epilogue of a 128-row tile)
 // waves per block: 128 x 128 in x3 / h2: eight (2 x 4); 128 x 32: two (2 x 1); everything else four (2 x 2)
 #define TRIS_NW(BM_, BN_, PREC_) ((BM_) == 128 && (BN_) == 128 && (PREC_) != 0 ? 8 : (BN_) == 32 ? 2 : 4)
 #define TRIS_FAST(BM_, BN_, EPI_, PREC_)                                                                       \
@@ -531,6 +535,8 @@ int run_cfg(GemmParams p, int batch, float* ws, hipStream_t st, Cfg cfg, int mod
       } else if (xtra) {                                                                           \
         if constexpr (AK == A_ROWK && (BKIND == B_NK || BKIND == B_KN)) TRIS_FAST_EPI(BM_, BN_, EPI_XTRA); \
         else return (int)hipErrorInvalidValue;                                                     \
+      } else if (pairx) {                                                                          \
+        if constexpr (AK == A_ROWK && (BKIND == B_NK || BKIND == B_KN)) TRIS_FAST_EPI(BM_, BN_, EPI_PAIR); \
       } else {                                                                                     \
         TRIS_FAST_EPI(BM_, BN_, EPI_STD);                                                          \
       }                                                                                            \
@@ -557,6 +563,8 @@ int run_cfg(GemmParams p, int batch, float* ws, hipStream_t st, Cfg cfg, int mod
     if (splitk > 1) {                                            \
       p.C = ws;                                                  \
       TRIS_PIPE_ONE(BM_, BN_, NW_, NWM_, EPI_SLAB);              \
+    } else if (pairx) {                                          \
+      if constexpr (AK == A_ROWK && (BKIND == B_NK || BKIND == B_KN)) TRIS_PIPE_ONE(BM_, BN_, NW_, NWM_, EPI_PAIR); \
     } else {                                                     \
       TRIS_PIPE_ONE(BM_, BN_, NW_, NWM_, EPI_STD);               \
     }                                                            \
@@ -566,6 +574,8 @@ int run_cfg(GemmParams p, int batch, float* ws, hipStream_t st, Cfg cfg, int mod
     if (splitk > 1) {                                                                                                            \
       p.C = ws;                                                                                                                  \
       hipLaunchKernelGGL((gemm_fast_kernel<BM_, BN_, AK, BKIND, EPI_SLAB, 4, NW_, 32, 4, NWM_>), grid, dim3(NW_ * 64), 0, st, p); \
+    } else if (pairx) {                                                                                                          \
+      hipLaunchKernelGGL((gemm_fast_kernel<BM_, BN_, AK, BKIND, EPI_PAIR, 4, NW_, 32, 4, NWM_>), grid, dim3(NW_ * 64), 0, st, p); \
     } else {                                                                                                                     \
       hipLaunchKernelGGL((gemm_fast_kernel<BM_, BN_, AK, BKIND, EPI_STD, 4, NW_, 32, 4, NWM_>), grid, dim3(NW_ * 64), 0, st, p);  \
     }                                                                                                                            \

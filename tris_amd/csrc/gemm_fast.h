@@ -895,6 +895,14 @@ void gemm_fast_kernel(GemmParams p) {
   unsigned e_am = 0u;   // largest magnitude stored (bits): by-product for p.amax_out
 #pragma unroll
   for (int j = 0; j < FN; ++j) vs_s[j] = vs_q[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  // the pooled residual and the third sum of the fused BatchNorm-backward reduction (p.resid_pool_h, p.bnb_x2): EPI_PAIR kernels only
+  // (the third sum lives in the vector epilogue alone: the products that carry it run 128-row tiles with 16-byte rows -- run_cfg checks
+  //  -- and every such EPI_PAIR kernel has the LDS turn-around; the one that has not, 64 x 64 in the f32 arithmetic, serves pooled residuals only)
+  constexpr bool PAIR = EPI == EPI_PAIR, BNB2 = PAIR && EPI_LDS;
+  static_assert(!PAIR || EPI_LDS || BM == 64, "an EPI_PAIR kernel with 128-row tiles without the vector epilogue");
+  float4 vs_q2[BNB2 ? FN : 1];
+#pragma unroll
+  for (int j = 0; j < (BNB2 ? FN : 1); ++j) vs_q2[j] = make_float4(0.f, 0.f, 0.f, 0.f);
   const bool vec_epi = EPI_LDS && p.vecC;  // uniform
   const bool nt_e = EPI != EPI_SLAB && p.nt != 0;   // uniform: epilogue streams larger than the memory-side cache (gemm_conv.hip stream_nt)
   if (vec_epi) {
@@ -930,6 +938,10 @@ void gemm_fast_kernel(GemmParams p) {
             nsc = make_float4(nis.x * ga.x, nis.y * ga.y, nis.z * ga.z, nis.w * ga.w);
           }
         }
+        float4 nmu2 = bc, nis2 = bc;
+        if constexpr (BNB2) {
+          if (p.bnb_x2 != nullptr && col < p.N) { nmu2 = ld4(p.bnb_mean2 + col); nis2 = ld4(p.bnb_invstd2 + col); }
+        }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const int row = grow(wm * WM + i * 32 + er + 8 * t);
@@ -950,7 +962,12 @@ void gemm_fast_kernel(GemmParams p) {
                 v.z = v.z / (1.0f + expf(-1.702f * v.z)); v.w = v.w / (1.0f + expf(-1.702f * v.w));
               }
               if (p.resid) {
-                const float4 rr = ld4s(p.resid + (long)zb * p.sR + (long)row * p.ldr + col, nt_e);
+                float4 rr;
+                if (PAIR && p.resid_pool_h) {   // (uniform) the gradient of a 2x2 average pool, read in place: avgpool2_bwd_kernel's value
+                  rr = ld4(p.resid + gp_pooled_row(row, p.resid_pool_h, p.resid_pool_w) * p.ldr + col);
+                  rr.x *= 0.25f; rr.y *= 0.25f; rr.z *= 0.25f; rr.w *= 0.25f;
+                } else
+                  rr = ld4s(p.resid + (long)zb * p.sR + (long)row * p.ldr + col, nt_e);
                 v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
               }
               if (p.bnb_x != nullptr) {
@@ -990,6 +1007,13 @@ void gemm_fast_kernel(GemmParams p) {
                 vs_s[j].x += v.x; vs_s[j].y += v.y; vs_s[j].z += v.z; vs_s[j].w += v.w;
                 vs_q[j].x += v.x * ((xx.x - nmu.x) * nis.x); vs_q[j].y += v.y * ((xx.y - nmu.y) * nis.y);
                 vs_q[j].z += v.z * ((xx.z - nmu.z) * nis.z); vs_q[j].w += v.w * ((xx.w - nmu.w) * nis.w);
+                if constexpr (BNB2) {
+                  if (p.bnb_x2 != nullptr) {
+                    const float4 x2 = ld4s(p.bnb_x2 + o, nt_e);
+                    vs_q2[j].x += v.x * ((x2.x - nmu2.x) * nis2.x); vs_q2[j].y += v.y * ((x2.y - nmu2.y) * nis2.y);
+                    vs_q2[j].z += v.z * ((x2.z - nmu2.z) * nis2.z); vs_q2[j].w += v.w * ((x2.w - nmu2.w) * nis2.w);
+                  }
+                }
               } else {
               if (EPI == EPI_XTRA && p.dact_x != nullptr) {
                 const float4 xg = ld4(p.dact_x + (long)row * p.ldc + col);
@@ -1026,7 +1050,9 @@ void gemm_fast_kernel(GemmParams p) {
             if (EPI == EPI_XTRA && p.pre_out != nullptr) p.pre_out[(long)row * p.ldc + col] = v;
             if (p.act == 1) v = fmaxf(v, 0.f);
             else if (p.act == 2) v = v / (1.0f + expf(-1.702f * v));
-            if (p.resid) v += p.resid[(long)zb * p.sR + (long)row * p.ldr + col];
+            if (p.resid)
+              v += (PAIR && p.resid_pool_h) ? p.resid[gp_pooled_row(row, p.resid_pool_h, p.resid_pool_w) * p.ldr + col] * 0.25f
+                                  : p.resid[(long)zb * p.sR + (long)row * p.ldr + col];
             if (EPI == EPI_XTRA && p.dact_x != nullptr) v = v * qgelu_grad(p.dact_x[(long)row * p.ldc + col]);
             if (p.bnb_x != nullptr) {   // (fused BatchNorm-backward reduction, scalar form: see the vector epilogue)
               const long o = (long)row * p.ldc + col;
@@ -1100,6 +1126,31 @@ void gemm_fast_kernel(GemmParams p) {
         for (int w = 0; w < NWM; ++w) { s += redd[(w * BN + tid) * 2]; q += redd[(w * BN + tid) * 2 + 1]; }
         o[n0 + tid] = s;
         o[p.N + n0 + tid] = q;
+      }
+      if constexpr (BNB2) {
+        if (p.bnb_x2 != nullptr) {    // (uniform) the third sum through the same scratch, into its own partial rows
+          __syncthreads();
+#pragma unroll
+          for (int j = 0; j < FN; ++j) {
+            double b[4] = {vs_q2[j].x, vs_q2[j].y, vs_q2[j].z, vs_q2[j].w};
+#pragma unroll
+            for (int sh = 8; sh < 64; sh <<= 1)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) b[e] += __shfl_xor(b[e], sh, 64);
+            if (lane < 8) {
+              const int cl = wn * WN + j * 32 + lane * 4;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) redd[(wm * BN + cl + e) * 2] = b[e];
+            }
+          }
+          __syncthreads();
+          if (tid < BN && n0 + tid < p.N) {
+            double q = 0.0;
+#pragma unroll
+            for (int w = 0; w < NWM; ++w) q += redd[(w * BN + tid) * 2];
+            p.stat_part2[(long)(tile / p.tiles_n) * 2 * p.N + n0 + tid] = q;
+          }
+        }
       }
       return;
     }

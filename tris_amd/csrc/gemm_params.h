@@ -4,7 +4,9 @@
 
 enum { A_ROWK = 0, A_COLK = 1, A_IM2COL = 2, A_HALO = 3 };  // A_HALO: direct 3x3 convolution (gemm_fast.h)
 enum { B_NK = 0, B_KN = 1, B_KN_DGRAD = 2, B_KN_IM2COL = 3 };
-enum { EPI_STD = 0, EPI_SLAB = 1, EPI_XTRA = 2 };   // EPI_XTRA: EPI_STD + the pre_out / dact_x extras (classic loop, row-major A)
+enum { EPI_STD = 0, EPI_SLAB = 1, EPI_XTRA = 2, EPI_PAIR = 3 };   // EPI_XTRA: EPI_STD + the pre_out / dact_x extras (classic loop, row-major A)
+// EPI_PAIR: EPI_STD + the pooled residual (resid_pool_*) + the third sum of the fused BatchNorm-backward reduction (bnb_x2): kernels of
+// their own (row-major A, every loop form), so that the products without either keep the registers of the EPI_STD kernels
 
 struct GemmParams {
   const float* A;
@@ -20,6 +22,10 @@ struct GemmParams {
   int bias_mode;  // 0 none, 1 per column n, 2 per row m
   const float* resid;
   long ldr, sR;
+  // pooled residual (EPI_PAIR, fast kernel, no split-K, batch 1; 0 = off): the rows of C are the pixels of a [B, resid_pool_h,
+  // resid_pool_w] map and resid holds the gradient of its 2x2 average pool, [B, h/2, w/2, N] -- the epilogue adds a quarter of the
+  // pooled pixel's value, i.e. exactly what avgpool2_bwd_kernel would have written to a full-size tensor first
+  int resid_pool_h, resid_pool_w;
   int act;  // 0 none, 1 relu, 2 quick-gelu
   float alpha;
   int vecA, vecB;  // 16-byte vector loads legal for the operand
@@ -43,6 +49,12 @@ struct GemmParams {
   // sum(dz), sum(dz * xhat) per column into stat_part [tiles_m][2][N] (fp64 across lanes / waves / tiles), i.e. exactly what
   // col_partial_kernel<1> computes in a pass of its own.
   const float *bnb_x, *bnb_y, *bnb_mean, *bnb_invstd, *bnb_gamma, *bnb_beta;
+  // ... optionally for a SECOND BatchNorm that receives the same masked gradient (the shortcut BatchNorm of a down-sampling Bottleneck
+  // beside its bn3): raw input bnb_x2 [M, N] (layout of C), its statistics, and sum(dz * xhat2) per column into the first N doubles of
+  // each row of stat_part2 [tiles_m][2][N] (the row layout of stat_part: the same finalizers read it).  Block-uniform; row-major
+  // A x (B_NK | B_KN) products only.  sum(dz) is the same number for both BatchNorms.
+  const float *bnb_x2, *bnb_mean2, *bnb_invstd2;
+  double* stat_part2;
   int bnb_y_pl;   // 1: bnb_y is an fp16-plane tensor (PREC 4 callers): its ReLU mask is "either piece non-zero"; 2: bnb_y is that mask itself, one
                   // byte per 8 columns (tris_bn_mask_next: written by the forward pass beside the planes)
   // PREC 3 ("h2": two fp16 pieces per operand, three f16 MFMAs per product): per-operand power-of-two scales, either derived in
@@ -86,6 +98,12 @@ __device__ __forceinline__ void st4s(float* p, float4 v, bool nt) {
   else *reinterpret_cast<float4*>(p) = v;
 }
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// row of the 2x2-pooled map [B, H/2, W/2] under pixel `row` of [B, H, W] (norm.hip pooled_row)
+__device__ __forceinline__ long gp_pooled_row(int row, int H, int W) {
+  const int x = row % W, t = row / W;
+  const int y = t % H, b = t / H;
+  return ((long)b * (H >> 1) + (y >> 1)) * (W >> 1) + (x >> 1);
+}
 
 // one launch configuration of the family: tile, split-K slices, pipe = 1: the pipelined loop of gemm_fast.h (x3 only: two 16-deep
 // LDS stages, one barrier per K tile; 256 x 128 tiles exist in that form only).  conv3_dispatch / the direct weight gradient

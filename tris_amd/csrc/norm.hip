@@ -281,7 +281,14 @@ __global__ __launch_bounds__(1024) void part_finalize_kernel(const T* __restrict
                                                             const float* __restrict__ gamma = nullptr, const float* __restrict__ invstd = nullptr,
                                                             float inv_cnt = 0.f, float xhat_max = 0.f,
                                                             const unsigned* __restrict__ dz_word = nullptr,
-                                                            unsigned* __restrict__ bound_out = nullptr) {
+                                                            unsigned* __restrict__ bound_out = nullptr,
+                                                            const T* __restrict__ part2 = nullptr, float* __restrict__ out0b = nullptr,
+                                                            float* __restrict__ out2 = nullptr, const float* __restrict__ gamma2 = nullptr,
+                                                            const float* __restrict__ invstd2 = nullptr,
+                                                            unsigned* __restrict__ bound_out2 = nullptr) {
+  // part2 != NULL (the pair of a down-sampling Bottleneck: bn3 and the shortcut BatchNorm receive the same masked gradient): the first
+  // C doubles of its rows hold sum(dz * xhat) of the SECOND BatchNorm; the launch also writes that sum to out2, sum(dz) a second time
+  // to out0b (that BatchNorm's dbeta) and the bound of its dx -- same expression, same dz amax word -- to bound_out2
   __shared__ float sh_adz;
   if (bound_out != nullptr && threadIdx.x < 64) {
     unsigned m = max(dz_word[threadIdx.x * 16], dz_word[(threadIdx.x + 64) * 16]);
@@ -293,12 +300,26 @@ __global__ __launch_bounds__(1024) void part_finalize_kernel(const T* __restrict
   int c;
   bool lead;
   reduce_parts(part, nb, C, out1 != nullptr, s, ss, c, lead);
+  double s2 = 0.0;
+  if (part2 != nullptr) {    // (uniform)
+    double none;
+    int c2;
+    bool lead2;
+    __syncthreads();         // (the leads have read the scratch of the first reduction)
+    reduce_parts(part2, nb, C, false, s2, none, c2, lead2);
+  }
   if (!lead) return;
   out0[c] = (float)s;
   if (out1) out1[c] = (float)ss;
   if (bound_out != nullptr)
     amax_raise(__builtin_bit_cast(unsigned, fabsf(gamma[c] * invstd[c]) * (sh_adz + fabsf((float)s) * inv_cnt + xhat_max * fabsf((float)ss) * inv_cnt)),
                bound_out);
+  if (part2 != nullptr) {
+    out0b[c] = (float)s;
+    out2[c] = (float)s2;
+    amax_raise(__builtin_bit_cast(unsigned, fabsf(gamma2[c] * invstd2[c]) * (sh_adz + fabsf((float)s) * inv_cnt + xhat_max * fabsf((float)s2) * inv_cnt)),
+               bound_out2);
+  }
 }
 
 // SyncBN: combine the per-rank statistics blocks [mean | invstd | biased var] (3*C floats each, exactly what
@@ -1090,6 +1111,21 @@ extern "C" int tris_part_finalize_bound_f32(const double* part, int rows, int C,
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(part_finalize_kernel<double>, dim3(fin_grid(C, rows)), dim3(fin_block(rows)), 0, (hipStream_t)stream, part, rows,
                      C, out0, out1, gamma, invstd, inv_count, xhat_max, dz_word, bound_out);
+  TRIS_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tris_part_finalize_pair_f32(const double* part, const double* part2, int rows, int C, float* sum_dz, float* sum_dzx,
+                                          float* sum_dz_b, float* sum_dzx2, const float* gamma, const float* invstd, const float* gamma2,
+                                          const float* invstd2, float inv_count, float xhat_max, const unsigned* dz_word,
+                                          unsigned* bound_out, unsigned* bound_out2, void* stream) {
+  if (rows < 1 || C < 1 || part == nullptr || part2 == nullptr || sum_dz == nullptr || sum_dzx == nullptr || sum_dz_b == nullptr ||
+      sum_dzx2 == nullptr || gamma == nullptr || invstd == nullptr || gamma2 == nullptr || invstd2 == nullptr || dz_word == nullptr ||
+      bound_out == nullptr || bound_out2 == nullptr || bound_out == bound_out2)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(part_finalize_kernel<double>, dim3(fin_grid(C, rows)), dim3(fin_block(rows)), 0, (hipStream_t)stream, part, rows,
+                     C, sum_dz, sum_dzx, gamma, invstd, inv_count, xhat_max, dz_word, bound_out, part2, sum_dz_b, sum_dzx2, gamma2,
+                     invstd2, bound_out2);
   TRIS_LAUNCH_CHECK();
   return 0;
 }

@@ -263,6 +263,79 @@ __global__ __launch_bounds__(256) void bn_apply_pl_kernel(const float* __restric
   pl_floor_commit(below, out_word);
 }
 
+// Y (planes, scale from out_word) = relu(bn3(X3) + bns(Xs)): the closing pass of a down-sampling Bottleneck with the shortcut's
+// BatchNorm inside it.  The two-launch chain -- bn_apply_kernel writing bns(Xs) as fp32, then bn_apply_pl_kernel reading it back as
+// its residual (rk 1) -- rounds the shortcut's value to fp32 (bn4's expression, plus the zero that stands in for its absent residual)
+// and adds it to bn3's value; the same two roundings in the same order here, so the planes (and the mask bytes) are the same bits.
+template <bool BIG>
+__global__ __launch_bounds__(256) void bn_apply_pair_pl_kernel(const float* __restrict__ X3, const float* __restrict__ mean3,
+                                                               const float* __restrict__ invstd3, const float* __restrict__ gamma3,
+                                                               const float* __restrict__ beta3, const float* __restrict__ Xs,
+                                                               const float* __restrict__ mean_s, const float* __restrict__ invstd_s,
+                                                               const float* __restrict__ gamma_s, const float* __restrict__ beta_s,
+                                                               float* __restrict__ Y, const unsigned* __restrict__ out_word, long n8, int C,
+                                                               unsigned char* __restrict__ mask_out) {
+  const float s = pl_scale(out_word);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool odd = lane & 1;
+  const long n = n8 * 8;
+  UnitWalk<BIG> w((n + 511) / 512, wave);
+  const int c = (int)((w.u * 512 + (odd ? 256 : 0) + 8 * (lane >> 1)) % C);
+  const Ch8 mu = ld8(mean3 + c), b = ld8(beta3 + c), mus = ld8(mean_s + c), bs = ld8(beta_s + c);
+  float4 sca, scb, ssa, ssb;
+  {
+    const Ch8 is = ld8(invstd3 + c), g = ld8(gamma3 + c), iss = ld8(invstd_s + c), gs = ld8(gamma_s + c);
+    sca = mul4(is.a, g.a); scb = mul4(is.b, g.b);
+    ssa = mul4(iss.a, gs.a); ssb = mul4(iss.b, gs.b);
+  }
+  const float4 z4 = make_float4(0, 0, 0, 0);
+  unsigned below = 0u;
+  auto finish = [&](long e0, float4 x0, float4 x1, float4 r0, float4 r1) {
+    const long e1 = e0 + 256;
+    pair_xchg(x0, x1, odd);
+    pair_xchg(r0, r1, odd);
+    float4 y0 = bn4(x0, mu.a, sca, b.a), y1 = bn4(x1, mu.b, scb, b.b);
+    r0 = add4(bn4(r0, mus.a, ssa, bs.a), z4);      // (bn_apply_kernel: ... + b + r with r = 0 where it has no residual)
+    r1 = add4(bn4(r1, mus.b, ssb, bs.b), z4);
+    y0 = relu4(add4(y0, r0));
+    y1 = relu4(add4(y1, r1));
+    below += pl_below_floor(y0, y1, s);
+    Pl8 o = pl8_split(y0, y1, s);
+    if (mask_out != nullptr) {     // (bn_apply_pl_kernel: one byte per group of 8 channels, tris_bn_mask_next)
+      const long eg = (e0 - lane * 4) + (odd ? 256 : 0) + 8 * (lane >> 1);
+      if (eg < n) mask_out[eg >> 3] = (unsigned char)pl8_positive(o.hi, o.lo);
+    }
+    pair_xchg(o.hi, o.lo, odd);
+    if (e0 < n) stu<BIG>(Y + e0, o.hi);
+    if (e1 < n) stu<BIG>(Y + e1, o.lo);
+  };
+  if (BIG) {
+    const long units = (n + 511) / 512;
+    for (long pb = blockIdx.x; pb * PL_UPB < units; pb += gridDim.x) {     // (pieces b, b + gridDim.x, ...: pl_big_blocks)
+      const long u0 = pb * PL_UPB + wave, uend = min(units, (pb + 1) * PL_UPB);
+      float4 x0[2], x1[2], r0[2], r1[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const long e0 = (u0 + 4 * q) * 512 + lane * 4, e1 = e0 + 256;
+        const bool ok0 = (u0 + 4 * q) < uend && e0 < n, ok1 = (u0 + 4 * q) < uend && e1 < n;
+        x0[q] = ok0 ? ldx<true>(X3 + e0) : z4;
+        x1[q] = ok1 ? ldx<true>(X3 + e1) : z4;
+        r0[q] = ok0 ? ldx<true>(Xs + e0) : z4;
+        r1[q] = ok1 ? ldx<true>(Xs + e1) : z4;
+      }
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+        if ((u0 + 4 * q) < uend) finish((u0 + 4 * q) * 512 + lane * 4, x0[q], x1[q], r0[q], r1[q]);   // (wave-uniform)
+    }
+  } else {
+    for (; w.u < w.end; w.u += w.step) {
+      const long e0 = w.u * 512 + lane * 4, e1 = e0 + 256;
+      finish(e0, e0 < n ? ldf4(X3 + e0) : z4, e1 < n ? ldf4(X3 + e1) : z4, e0 < n ? ldf4(Xs + e0) : z4, e1 < n ? ldf4(Xs + e1) : z4);
+    }
+  }
+  pl_floor_commit(below, out_word);
+}
+
 // Yp (planes) = avgpool2(relu(bn(X)))  (norm.hip bn_apply_pool_kernel's expression on the four normalised pixels)
 __global__ __launch_bounds__(256) void bn_apply_pool_pl_kernel(const float* __restrict__ X, const float* __restrict__ mean,
                                                                const float* __restrict__ invstd, const float* __restrict__ gamma,
@@ -458,6 +531,92 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pl_kernel(const float* __res
   pl_floor_commit(below, out_word);
 }
 
+// dX3, dXs (planes, each at the scale of its own word) from ONE read of the masked gradient dZ that bn3 and the shortcut BatchNorm of a
+// down-sampling Bottleneck both receive: bn_bwd_apply_pl_kernel's arithmetic (no mask: dZ arrives masked) for each of the two, with
+// the shared sum_dz.  Given the same sums the planes are those of two tris_bn_bwd_apply_pl_f32 launches, bit for bit.
+template <bool BIG>
+__global__ __launch_bounds__(256) void bn_bwd_apply_pair_pl_kernel(const float* __restrict__ dZ, const float* __restrict__ X3,
+                                                                   const float* __restrict__ mean3, const float* __restrict__ invstd3,
+                                                                   const float* __restrict__ gamma3, const float* __restrict__ sum_dzx3,
+                                                                   const float* __restrict__ Xs, const float* __restrict__ mean_s,
+                                                                   const float* __restrict__ invstd_s, const float* __restrict__ gamma_s,
+                                                                   const float* __restrict__ sum_dzx_s, const float* __restrict__ sum_dz,
+                                                                   float inv_cnt, float* __restrict__ dX3, const unsigned* __restrict__ word3,
+                                                                   float* __restrict__ dXs, const unsigned* __restrict__ word_s, long n8, int C) {
+  const float s3 = pl_scale(word3), ss = pl_scale(word_s);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool odd = lane & 1;
+  const long n = n8 * 8;
+  UnitWalk<BIG> w((n + 511) / 512, wave);
+  const int c = (int)((w.u * 512 + (odd ? 256 : 0) + 8 * (lane >> 1)) % C);
+  struct K { Ch8 mu; float4 k1a, k1b, k3a, k3b; };
+  auto consts = [&](const float* mean, const float* invstd, const float* gamma, const float* sdzx) {
+    K k;
+    k.mu = ld8(mean + c);
+    const Ch8 is = ld8(invstd + c), ga = ld8(gamma + c), sb = ld8(sdzx + c);
+    k.k1a = mul4(ga.a, is.a); k.k1b = mul4(ga.b, is.b);
+    k.k3a = make_float4(is.a.x * sb.a.x * inv_cnt, is.a.y * sb.a.y * inv_cnt, is.a.z * sb.a.z * inv_cnt, is.a.w * sb.a.w * inv_cnt);
+    k.k3b = make_float4(is.b.x * sb.b.x * inv_cnt, is.b.y * sb.b.y * inv_cnt, is.b.z * sb.b.z * inv_cnt, is.b.w * sb.b.w * inv_cnt);
+    return k;
+  };
+  const K a3 = consts(mean3, invstd3, gamma3, sum_dzx3), as = consts(mean_s, invstd_s, gamma_s, sum_dzx_s);
+  const Ch8 sa = ld8(sum_dz + c);
+  const float4 k2a = make_float4(sa.a.x * inv_cnt, sa.a.y * inv_cnt, sa.a.z * inv_cnt, sa.a.w * inv_cnt);
+  const float4 k2b = make_float4(sa.b.x * inv_cnt, sa.b.y * inv_cnt, sa.b.z * inv_cnt, sa.b.w * inv_cnt);
+  const float4 z4 = make_float4(0, 0, 0, 0);
+  unsigned below3 = 0u, below_s = 0u;
+  auto half = [&](const float4 g, const float4 x, const float4 mu4, const float4 k1, const float4 k2, const float4 k3) {
+    return make_float4(k1.x * (g.x - k2.x - (x.x - mu4.x) * k3.x), k1.y * (g.y - k2.y - (x.y - mu4.y) * k3.y),
+                       k1.z * (g.z - k2.z - (x.z - mu4.z) * k3.z), k1.w * (g.w - k2.w - (x.w - mu4.w) * k3.w));
+  };
+  auto one = [&](long e0, const float4 g0, const float4 g1, float4 x0, float4 x1, const K& k, const float s, unsigned& below, float* dX) {
+    const long e1 = e0 + 256;
+    pair_xchg(x0, x1, odd);
+    const float4 o0 = half(g0, x0, k.mu.a, k.k1a, k2a, k.k3a), o1 = half(g1, x1, k.mu.b, k.k1b, k2b, k.k3b);
+    below += pl_below_floor(o0, o1, s);
+    Pl8 o = pl8_split(o0, o1, s);
+    pair_xchg(o.hi, o.lo, odd);
+    if (e0 < n) stu<BIG>(dX + e0, o.hi);
+    if (e1 < n) stu<BIG>(dX + e1, o.lo);
+  };
+  auto finish = [&](long e0, float4 g0, float4 g1, const float4 x0, const float4 x1, const float4 r0, const float4 r1) {
+    pair_xchg(g0, g1, odd);
+    one(e0, g0, g1, x0, x1, a3, s3, below3, dX3);
+    one(e0, g0, g1, r0, r1, as, ss, below_s, dXs);
+  };
+  if (BIG) {
+    const long units = (n + 511) / 512;
+    for (long pb = blockIdx.x; pb * PL_UPB < units; pb += gridDim.x) {     // (pieces b, b + gridDim.x, ...: pl_big_blocks)
+      const long u0 = pb * PL_UPB + wave, uend = min(units, (pb + 1) * PL_UPB);
+      float4 g0[2], g1[2], x0[2], x1[2], r0[2], r1[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const long u = u0 + 4 * q;
+        const long e0 = u * 512 + lane * 4, e1 = e0 + 256;
+        const bool ok0 = u < uend && e0 < n, ok1 = u < uend && e1 < n;
+        g0[q] = ok0 ? ldx<true>(dZ + e0) : z4;
+        g1[q] = ok1 ? ldx<true>(dZ + e1) : z4;
+        x0[q] = ok0 ? ldx<true>(X3 + e0) : z4;
+        x1[q] = ok1 ? ldx<true>(X3 + e1) : z4;
+        r0[q] = ok0 ? ldx<true>(Xs + e0) : z4;
+        r1[q] = ok1 ? ldx<true>(Xs + e1) : z4;
+      }
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+        if ((u0 + 4 * q) < uend) finish((u0 + 4 * q) * 512 + lane * 4, g0[q], g1[q], x0[q], x1[q], r0[q], r1[q]);
+    }
+  } else {
+    for (; w.u < w.end; w.u += w.step) {
+      const long e0 = w.u * 512 + lane * 4, e1 = e0 + 256;
+      const bool ok0 = e0 < n, ok1 = e1 < n;
+      finish(e0, ok0 ? ldf4(dZ + e0) : z4, ok1 ? ldf4(dZ + e1) : z4, ok0 ? ldf4(X3 + e0) : z4, ok1 ? ldf4(X3 + e1) : z4,
+             ok0 ? ldf4(Xs + e0) : z4, ok1 ? ldf4(Xs + e1) : z4);
+    }
+  }
+  pl_floor_commit(below3, word3);
+  pl_floor_commit(below_s, word_s);
+}
+
 // amax words that are bounds (one block; only line 0 of the word is written, the others stay zero -- the caller zeroes the word)
 __global__ __launch_bounds__(256) void bn_out_bound2_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, int C,
                                                             float xhat_max, const unsigned* __restrict__ add_word,
@@ -537,6 +696,27 @@ extern "C" int tris_bn_apply_pl_f32(const float* X, const float* mean, const flo
   TRIS_LAUNCH_CHECK();
   return 0;
 }
+extern "C" int tris_bn_apply_pair_pl_f32(const float* X3, const float* mean3, const float* invstd3, const float* gamma3,
+                                         const float* beta3, const float* Xs, const float* mean_s, const float* invstd_s,
+                                         const float* gamma_s, const float* beta_s, float* Ypl, const unsigned* out_word, long M, int C,
+                                         void* stream) {
+  unsigned char* const mask = g_bn_mask_next;     // (taken first thing, like tris_bn_apply_pl_f32: an arming never outlives its call)
+  g_bn_mask_next = nullptr;
+  if (C <= 0 || C % 8 || 2048 % C || M <= 0 || out_word == nullptr || X3 == nullptr || Xs == nullptr || Ypl == nullptr ||
+      mean3 == nullptr || invstd3 == nullptr || gamma3 == nullptr || beta3 == nullptr || mean_s == nullptr || invstd_s == nullptr ||
+      gamma_s == nullptr || beta_s == nullptr || !al16p(X3) || !al16p(Xs) || !al16p(Ypl) || !al16p(mean3) || !al16p(invstd3) ||
+      !al16p(gamma3) || !al16p(beta3) || !al16p(mean_s) || !al16p(invstd_s) || !al16p(gamma_s) || !al16p(beta_s))
+    return (int)hipErrorInvalidValue;
+  const long n8 = M * C / 8;
+  if (pl_big(n8, C, 3))       // (three streams, as the residual form of tris_bn_apply_pl_f32 it replaces)
+    hipLaunchKernelGGL(bn_apply_pair_pl_kernel<true>, dim3(pl_big_blocks(n8)), dim3(256), 0, (hipStream_t)stream, X3, mean3, invstd3,
+                       gamma3, beta3, Xs, mean_s, invstd_s, gamma_s, beta_s, Ypl, out_word, n8, C, mask);
+  else
+    hipLaunchKernelGGL(bn_apply_pair_pl_kernel<false>, dim3(pl_grid(n8, C)), dim3(256), 0, (hipStream_t)stream, X3, mean3, invstd3,
+                       gamma3, beta3, Xs, mean_s, invstd_s, gamma_s, beta_s, Ypl, out_word, n8, C, mask);
+  TRIS_LAUNCH_CHECK();
+  return 0;
+}
 extern "C" int tris_bn_apply_pool_pl_f32(const float* X, const float* mean, const float* invstd, const float* gamma, const float* beta,
                                          float* Ypl, const unsigned* out_word, int B, int H, int W, int C, void* stream) {
   if (C % 8 || (H & 1) || (W & 1) || out_word == nullptr || !al16p(X) || !al16p(Ypl)) return (int)hipErrorInvalidValue;
@@ -565,6 +745,28 @@ extern "C" int tris_bn_bwd_apply_pl_f32(const float* dY, const float* Ypl, const
   else
     hipLaunchKernelGGL((bn_bwd_apply_pl_kernel<false, false>), dim3(pl_grid(n8, C)), dim3(256), 0, (hipStream_t)stream, dY, Ypl, X, mean,
                        invstd, gamma, sum_dz, sum_dzx, inv_count, dXpl, out_word, dZ, n8, C, beta_mask, 0, 0);
+  TRIS_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int tris_bn_bwd_apply_pair_pl_f32(const float* dZ, const float* X3, const float* mean3, const float* invstd3, const float* gamma3,
+                                            const float* sum_dzx3, const float* Xs, const float* mean_s, const float* invstd_s,
+                                            const float* gamma_s, const float* sum_dzx_s, const float* sum_dz, float inv_count,
+                                            float* dX3pl, const unsigned* word3, float* dXspl, const unsigned* word_s, long M, int C,
+                                            void* stream) {
+  const void* ptrs[] = {dZ, X3, mean3, invstd3, gamma3, sum_dzx3, Xs, mean_s, invstd_s, gamma_s, sum_dzx_s, sum_dz, dX3pl, dXspl};
+  for (const void* q : ptrs)
+    if (q == nullptr || !al16p(q)) return (int)hipErrorInvalidValue;
+  if (C <= 0 || C % 8 || 2048 % C || M <= 0 || word3 == nullptr || word_s == nullptr || word3 == word_s || dX3pl == dXspl)
+    return (int)hipErrorInvalidValue;
+  const long n8 = M * C / 8;
+  if (pl_big(n8, C, 5))
+    hipLaunchKernelGGL(bn_bwd_apply_pair_pl_kernel<true>, dim3(pl_big_blocks(n8)), dim3(256), 0, (hipStream_t)stream, dZ, X3, mean3,
+                       invstd3, gamma3, sum_dzx3, Xs, mean_s, invstd_s, gamma_s, sum_dzx_s, sum_dz, inv_count, dX3pl, word3, dXspl,
+                       word_s, n8, C);
+  else
+    hipLaunchKernelGGL(bn_bwd_apply_pair_pl_kernel<false>, dim3(pl_grid(n8, C)), dim3(256), 0, (hipStream_t)stream, dZ, X3, mean3,
+                       invstd3, gamma3, sum_dzx3, Xs, mean_s, invstd_s, gamma_s, sum_dzx_s, sum_dz, inv_count, dX3pl, word3, dXspl,
+                       word_s, n8, C);
   TRIS_LAUNCH_CHECK();
   return 0;
 }

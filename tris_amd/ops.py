@@ -498,8 +498,11 @@ class batch_invariant:
 
 
 def gemm(A, B, C, M, N, K, lda, ldb, ldc, tA, tB, batch=1, sA=0, sB=0, sC=0, bias=None, bias_mode=0, resid=None,
-         ldr=0, sR=0, act=0, alpha=1.0, use_ws=True, pre_out=None, dact=None, w_a=False, w_b=False, w_bt=False, mark=True):
-    """pre_out / dact (tris_gemm_epilogue_next): also store the pre-activation value / multiply the result by quickgelu'(dact);
+         ldr=0, sR=0, act=0, alpha=1.0, use_ws=True, pre_out=None, dact=None, w_a=False, w_b=False, w_bt=False, mark=True,
+         resid_pool=None):
+    """resid_pool = (H, W) (tris_gemm_resid_pool_next): resid is the gradient of the 2x2 average pool of the [.., H, W] map the rows
+    of C stand for; the call returns False -- nothing launched -- where the fast kernel does not serve the product (caller falls back).
+    pre_out / dact (tris_gemm_epilogue_next): also store the pre-activation value / multiply the result by quickgelu'(dact);
     the call then returns False -- nothing launched -- when the fast kernel does not serve the operands (caller falls back).
     w_a / w_b: that operand is a convolution weight, which exists as operand planes when the other operand is a plane tensor.
     mark=False: no product will read C as an operand (a weight gradient written into the optimiser's arena): the launch -- and the
@@ -549,13 +552,15 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, tA, tB, batch=1, sA=0, sB=0, sC=0, bia
         tk = splitk_tickets()
         if tk is not None:
             call("tris_splitk_tickets_next", tk.data_ptr(), tk.numel())
-    _timed("gemm", 2.0 * M * N * K * batch, lambda: call(
+    if resid_pool is not None:
+        call("tris_gemm_resid_pool_next", resid_pool[0], resid_pool[1])
+    ran = _timed("gemm", 2.0 * M * N * K * batch, lambda: (_declinable if resid_pool is not None else call)(
         "tris_gemm_f32", pA, pB, P(C), M, N, K, lda, ldb, ldc, int(tA), int(tB), batch, sA, sB, sC, P(bias),
         bias_mode, P(resid), ldr, sR, act, float(alpha), P(ws), 0 if ws is None else ws.numel() * 4, _stream()),
         tag=(f"{'T' if tA else 'N'}{'T' if tB else 'N'} M{M} N{N} K{K} b{batch}" if _PROF_SHAPES else None),
         nbytes=4.0 * ((M * K if (sA == 0 and batch > 1) else batch * M * K) + batch * K * N
                       + batch * M * N * (2 if resid is not None else 1)))
-    return C
+    return False if ran is False else C
 
 
 def colsum(X, M, N, out):
@@ -615,12 +620,15 @@ class GradBox:
 
     In the down-sampling Bottlenecks the second consumer of x is the shortcut (avg-pool / 1x1 conv); its backward normally
     runs before conv1's too (autograd schedules later-created nodes first) but nothing guarantees it, so the depositor
-    checks `consumed` and simply returns its gradient to autograd if conv1 has already run."""
-    __slots__ = ("value", "consumed")
+    checks `consumed` and simply returns its gradient to autograd if conv1 has already run.
+    `pool` = (H, W): the value is the gradient of the 2x2 average pool of x (a stride-2 shortcut, cfg.bn_pair), a quarter of the size;
+    conv1's epilogue reads it at the pooled pixel (tris_gemm_resid_pool_next) instead of a full-size expansion written for it."""
+    __slots__ = ("value", "consumed", "pool")
 
     def __init__(self):
         self.value = None
         self.consumed = False
+        self.pool = None
 
     def deposit(self, g):
         """-> True if the gradient was taken over (the caller must then return None for that input)"""
@@ -1222,7 +1230,7 @@ class _BnBwdLink:
     on whatever arrived, which is why the masked gradient is only ever produced when the BatchNorm is known to be behind it.
     The model marks the BatchNorms whose output has exactly one autograd consumer (Bottleneck: bn2 -> conv3; bn3 -> the next
     block's conv1, the residual branch rides a GradBox) with bwd_link=True."""
-    __slots__ = ("x", "mean", "invstd", "gamma", "beta", "from_y", "dz", "part", "rows", "dzw", "mask")
+    __slots__ = ("x", "mean", "invstd", "gamma", "beta", "from_y", "dz", "part", "rows", "dzw", "mask", "pair", "part2")
 
     def __init__(self, x, mean, invstd, gamma, beta, from_y):
         # (no reference to the BatchNorm's OUTPUT, which carries this object: the consumer has that tensor as its own input)
@@ -1230,11 +1238,15 @@ class _BnBwdLink:
         self.dz = self.part = self.dzw = None
         self.rows = 0
         self.mask = None      # (cfg.bn_bitmask) the ReLU mask of the BatchNorm's plane output, one byte per 8 channels (tris_bn_mask_next)
+        # (cfg.bn_pair) bn3 of a down-sampling Bottleneck: the `_bn_pair` hand-over of its shortcut BatchNorm, which receives the same
+        # masked gradient -- the product also reduces sum(dz * xhat_s) (tris_gemm_bnbwd_x2_next), into part2
+        self.pair = self.part2 = None
 
-    def fill(self, dz, part, rows, dzw=None):
+    def fill(self, dz, part, rows, dzw=None, part2=None):
         # (identity of the gradient tensor, not a reference to it: autograd hands a sole-owner gradient on without a copy)
         # dzw: amax word of the masked gradient (operand planes: the bound of the BatchNorm's dx is formed from it)
         self.dz, self.part, self.rows, self.dzw = (dz.data_ptr(), dz._version, tuple(dz.shape)), part, rows, dzw
+        self.part2 = part2
 
     def take(self, dy):
         """(part, rows) if dy IS the masked gradient this link's product left (same storage, version and shape); None if no product
@@ -1242,11 +1254,11 @@ class _BnBwdLink:
         down-sampling block whose shortcut backward ran late, a model that uses the BatchNorm output twice).  The caller then runs
         the usual two passes on whatever arrived, which is correct for any sum of gradients (the ReLU mask is idempotent: masking
         an already-masked term again changes nothing).  One use."""
-        dz, part, rows, dzw = self.dz, self.part, self.rows, self.dzw
-        self.dz = self.part = self.dzw = None
+        dz, part, rows, dzw, part2 = self.dz, self.part, self.rows, self.dzw, self.part2
+        self.dz = self.part = self.dzw = self.part2 = None
         if dz is None or (dy.data_ptr(), dy._version, tuple(dy.shape)) != dz:
             return None
-        return part, rows, dzw
+        return part, rows, dzw, part2
 
 
 def _bn_bwd_fuse_enabled():
@@ -1313,10 +1325,12 @@ class LinearFn(torch.autograd.Function):
         dx = None
         box = ctx.grad_box
         extra = None   # a residual-branch gradient left by a later layer of the same block: added in the GEMM epilogue
+        pool = None    # ... given as the gradient of its 2x2 average pool (GradBox.pool)
         if box is not None:
             box.consumed = True
             if box.value is not None:
                 extra, box.value = box.value, None
+                pool, box.pool = box.pool, None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             link, fused = ctx.bn_link, False
@@ -1329,7 +1343,11 @@ class LinearFn(torch.autograd.Function):
                 part = torch.empty(((M + 127) // 128) * 2 * K, device=x.device, dtype=torch.float64)
                 rows = ctypes.c_int(0)
                 ypl = link.from_y and pl_word(x) is not None   # (the BatchNorm's output as planes: only a plane product masks from it)
+                pr2 = link.pair if (cfg.bn_pair and "bwd" in cfg.bn_pair_parts and planes_on()) else None
+                part2 = None
                 if not ypl or pl_word(dy) is not None:
+                    if pr2 is not None:
+                        part2 = torch.empty_like(part)     # (the shortcut BatchNorm's sum(dz * xhat_s), same rows)
                     dzw = _h2_slot() if planes_on() else None   # (the masked gradient's amax: the bound of that BatchNorm's dx)
 
                     def launch():
@@ -1340,6 +1358,10 @@ class LinearFn(torch.autograd.Function):
                         by = (P(x) if (PL_STATS["last"] or not ypl) else P(unplanes(x))) if link.from_y else None
                         if bits and PL_STATS["last"]:
                             by = link.mask.data_ptr()       # (the product took planes and was armed with flag 4: bn_y is the byte mask)
+                        if pool is not None:
+                            call("tris_gemm_resid_pool_next", pool[0], pool[1])
+                        if part2 is not None:
+                            call("tris_gemm_bnbwd_x2_next", P(pr2[0]), P(pr2[1]), P(pr2[2]), part2.data_ptr())
                         call("tris_gemm_bnbwd_f32", pp[0], pp[1], P(dx), M, K, N, P(extra), K, P(link.x), by,
                              P(link.mean), P(link.invstd), P(link.gamma), P(link.beta), part.data_ptr(), ctypes.byref(rows), _stream())
                         return rows.value > 0     # (False: the entry point declined the shape, nothing was launched)
@@ -1347,13 +1369,18 @@ class LinearFn(torch.autograd.Function):
                            nbytes=4.0 * (M * N + N * K + M * K * (2 + int(link.from_y) + int(extra is not None))))
                     if rows.value > 0:
                         fused = True
-                        link.fill(dx, part, rows.value, dzw)
+                        link.fill(dx, part, rows.value, dzw, part2)
             alink = ctx.act_link
             if not fused and alink is not None and extra is None:
                 # x = QuickGELU(pre) with this product as its only consumer (linear_qgelu): the data gradient comes out of the
                 # epilogue already multiplied by quickgelu'(pre); the producer's backward is told so
                 if gemm(dy, w, dx, M, K, N, N, K, K, False, False, dact=alink.pre) is not False:
                     fused = alink.applied = True
+            if not fused and pool is not None:
+                if gemm(dy, w, dx, M, K, N, N, K, K, False, False, resid=extra, ldr=K, w_b=True, w_bt=True, resid_pool=pool) is False:
+                    extra = _avgpool2_bwd(extra, x.shape)    # (a product the fast kernel does not serve: the expansion after all)
+                else:
+                    fused = True
             if not fused:
                 gemm(dy, w, dx, M, K, N, N, K, K, False, False, resid=extra, ldr=K, w_b=True, w_bt=True)
         elif extra is not None:
@@ -1694,9 +1721,12 @@ class BatchNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, rmean, rvar, resid, relu, training, momentum, eps, group, part=None, grad_box=None,
-                lazy=False, bwd_link=False, pool=False, planes=False, dx_planes=False):
+                lazy=False, bwd_link=False, pool=False, planes=False, dx_planes=False, pair=False):
         """planes: the output is WRITTEN as fp16 operand planes (every consumer is a product, a plane-aware BatchNorm / pool, or goes
-        through ops.unplanes); dx_planes: so is the input gradient (its one consumer is the backward of the convolution before)."""
+        through ops.unplanes); dx_planes: so is the input gradient (its one consumer is the backward of the convolution before).
+        pair (the shortcut BatchNorm of a down-sampling Bottleneck; cfg.bn_pair): the output's ONLY reader is the block's bn3, as its
+        residual -- where the plane path applies the statistics are formed here, the output is NOT written, and what comes back is an
+        unallocated stand-in carrying `_bn_pair`; bn3's pass normalises the shortcut's raw input itself (tris_bn_apply_pair_pl_f32)"""
         _chk(x, gamma, beta, rmean, rvar, resid)
         y_mask = None
         x = x.contiguous()
@@ -1706,12 +1736,24 @@ class BatchNormFn(torch.autograd.Function):
         ctx.dx_pl = bool(dx_planes and training and C % 8 == 0 and 2048 % C == 0 and planes_on())
         if use_pl:
             lazy = False
+        pair_out = bool(pair and cfg.bn_pair and "fwd" in cfg.bn_pair_parts and training and group is None and resid is None and not relu
+                        and not pool and not lazy and not use_pl and C % 8 == 0 and 2048 % C == 0 and planes_on())
+        pr = getattr(resid, "_bn_pair", None) if resid is not None else None     # (bn3 of that block: the shortcut to normalise)
+        if pr is not None and not (use_pl and group is None and relu and not pool and pr[0].shape == x.shape):
+            resid, pr = _bn_pair_write(pr), None     # (this BatchNorm cannot take the pair: the shortcut's output as it used to be)
         # pool: the output is avgpool2(relu(bn(x))) -- BatchNorm + ReLU + AvgPool2d(2) as one op, the full-size tensor never written
         pool = bool(pool)   # (ops.batch_norm has checked: train mode, ReLU, no residual, even map)
         y = (torch.empty(x.shape[0], x.shape[1] // 2, x.shape[2] // 2, C, device=x.device, dtype=torch.float32) if pool
-             else torch.empty_like(x))
-        if resid is not None:
+             else (None if pair_out else torch.empty_like(x)))
+        if resid is not None and pr is None:
             resid = resid.contiguous()
+
+        def resid_word():
+            """amax word of the residual: its plane word, the bound of a paired shortcut, else its amax (a by-product or a pre-pass)"""
+            if pr is not None:
+                return pr[5]
+            w = pl_word(resid)
+            return w if w is not None else _h2_amax(resid)
         count = M
         if training:
             stats = torch.empty(3 * C, device=x.device, dtype=torch.float32)
@@ -1720,13 +1762,12 @@ class BatchNormFn(torch.autograd.Function):
 
             def local_stats(rm, rv, dst=None):
                 dst = stats if dst is None else dst
-                if part is not None and use_pl and group is None:
+                if part is not None and (use_pl or pair_out) and group is None:
                     # partial sums from the producing conv's epilogue; the same launch leaves the bound of the plane output
+                    # (pair_out: the bound of the shortcut's value, which bn3's launch chains into its own as add_word)
                     w_, rw_ = _h2_slot(), None
                     if resid is not None:
-                        rw_ = pl_word(resid)
-                        if rw_ is None:
-                            rw_ = _h2_amax(resid)
+                        rw_ = resid_word()
                     if w_ is not None and (resid is None or rw_ is not None):
                         call("tris_bn_finalize_bound_f32", part[0].data_ptr(), part[1], M, C, eps, momentum, P(dst), P(rm), P(rv),
                              P(gamma), P(beta), math.sqrt(max(M - 1, 1)), rw_, w_, _stream())
@@ -1751,9 +1792,7 @@ class BatchNormFn(torch.autograd.Function):
                     if use_pl and cfg.syncbn_bound:   # ... + the bound word of the plane output (what tris_bn_out_bound2_f32 would launch for)
                         w_ = _h2_slot()
                         if resid is not None:
-                            rw_ = pl_word(resid)
-                            if rw_ is None:
-                                rw_ = _h2_amax(resid)
+                            rw_ = resid_word()
                     if w_ is not None and (resid is None or rw_ is not None):
                         mb.bn_combine_bound(loc, C, M, eps, momentum, stats, rmean, rvar, gamma, beta,
                                             math.sqrt(max(M * world - 1, 1)), rw_, w_)
@@ -1775,7 +1814,20 @@ class BatchNormFn(torch.autograd.Function):
         lazy = bool(lazy and training and relu and resid is None)
         if not use_pl and resid is not None:
             resid = unplanes(resid)
-        if use_pl:
+        if pair_out and pl_bound["word"] is None:
+            # (statistics from a pass of their own -- a convolution too small for the fused epilogue: the bound in a launch of its own)
+            pl_bound["word"] = _h2_slot()
+            if pl_bound["word"] is not None:
+                call("tris_bn_out_bound2_f32", P(gamma), P(beta), C, math.sqrt(max(count - 1, 1)), None, pl_bound["word"], _stream())
+            else:                                      # (no amax word left in the pool: the shortcut is written after all)
+                pair_out, y = False, torch.empty_like(x)
+        if pair_out:
+            # neither allocated nor written: autograd needs a tensor of the output's shape to route bn3's residual gradient back here
+            y = torch.empty(1, device=x.device, dtype=torch.float32).expand(x.shape)
+            # (the dict: what bn3's backward needs to know of this BatchNorm's, and where it leaves dx and the sums it formed for it)
+            ctx.pair_state = {"dx_pl": ctx.dx_pl, "needs": tuple(ctx.needs_input_grad[:3])}
+            y._bn_pair = (x, mean, invstd, gamma, beta, pl_bound["word"], ctx.pair_state)
+        elif use_pl:
             # the scale must exist before the pass writes: Samuelson's bound of the normalised values from the affine parameters,
             # plus the bound (or amax) of the residual it is added to
             rk = 0 if resid is None else (2 if pl_word(resid) is not None else 1)
@@ -1784,9 +1836,7 @@ class BatchNormFn(torch.autograd.Function):
             if word is None:
                 word = _h2_slot()
                 if resid is not None:
-                    rw = pl_word(resid)
-                    if rw is None:
-                        rw = _h2_amax(resid)
+                    rw = resid_word()
                 if word is None or (resid is not None and rw is None):
                     raise RuntimeError("operand planes: no amax word for a BatchNorm output / its residual")
                 call("tris_bn_out_bound2_f32", P(gamma), P(beta), C, math.sqrt(max(count - 1, 1)), rw, word, _stream())
@@ -1799,8 +1849,12 @@ class BatchNormFn(torch.autograd.Function):
                     # the pass also leaves the mask as one byte per 8 channels, so that epilogue reads a bit, not the plane element
                     y_mask = torch.empty(M * C // 8, device=x.device, dtype=torch.uint8)
                     call("tris_bn_mask_next", y_mask.data_ptr())
-                call("tris_bn_apply_pl_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(resid), rk, rw if rk == 2 else None, P(y),
-                     word, M, C, int(relu), _stream())
+                if pr is not None:   # relu(bn3(x) + bn_s(xs)): the shortcut's BatchNorm in the same pass
+                    call("tris_bn_apply_pair_pl_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(pr[0]), P(pr[1]), P(pr[2]), P(pr[3]),
+                         P(pr[4]), P(y), word, M, C, _stream())
+                else:
+                    call("tris_bn_apply_pl_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(resid), rk, rw if rk == 2 else None,
+                         P(y), word, M, C, int(relu), _stream())
             pl_tag(y, word)
         elif pool:
             h2_mark_next(y)
@@ -1819,6 +1873,9 @@ class BatchNormFn(torch.autograd.Function):
         ctx.params = (gamma, beta)
         ctx.training = bool(training)
         ctx.link = None
+        ctx.pair = pr
+        if not pair_out:
+            ctx.pair_state = None
         ctx.pool = pool
         ctx.y_pl = getattr(y, "_pl", None)
         if training:
@@ -1828,6 +1885,7 @@ class BatchNormFn(torch.autograd.Function):
                 # the consumer (ops.linear) may reduce this BatchNorm's backward sums in its data-gradient epilogue: _BnBwdLink
                 ctx.link = y._bn_link = _BnBwdLink(x, mean, invstd, gamma, beta, keep_y)
                 ctx.link.mask = y_mask if keep_y else None
+                ctx.link.pair = pr if keep_y else None
         return y
 
     @staticmethod
@@ -1836,6 +1894,15 @@ class BatchNormFn(torch.autograd.Function):
             raise NotImplementedError("BatchNorm in eval mode is forward-only on this path")
         x, gamma, beta, mean, invstd, y = ctx.saved_tensors
         M, C, relu, has_res, count, group = ctx.cfg
+        done = ctx.pair_state.pop("done", None) if ctx.pair_state is not None else None
+        if done is not None:
+            # the shortcut BatchNorm of a pair whose bn3 backward has done this one's as well (below): dx is written, the sums formed
+            dxs, in_arena_s, sums_s = done
+            dg = db = None
+            if not in_arena_s:
+                dg = _emit(ctx.params[0], lambda o: o.copy_(sums_s[C:]), ctx.needs_input_grad[1])
+                db = _emit(ctx.params[1], lambda o: o.copy_(sums_s[:C]), ctx.needs_input_grad[2])
+            return (dxs, dg, db) + (None,) * 16
         dy = unplanes(pl_grad_in(dy.contiguous()))   # (the gradient of a BatchNorm OUTPUT is fp32 on every path of the trunk)
         _retag(y, ctx.y_pl)
         y_is_pl = pl_word(y) is not None
@@ -1881,7 +1948,21 @@ class BatchNormFn(torch.autograd.Function):
         bound_word = None     # (operand planes: dx's bound word when the finalizer below formed it)
         if got is not None and dx_pl and mb is None and (direct or group is None) and ctx.needs_input_grad[0]:
             bound_word = _h2_slot()
-        if got is not None and bound_word is not None:
+        # cfg.bn_pair: the product that left bn3's sums also left sum(dz * xhat_s) of the shortcut BatchNorm, which receives the same
+        # masked gradient: one finalizer launch for both, one apply pass that reads dz once and writes both input gradients
+        pair, pair_word = ctx.pair, None
+        if (pair is not None and got is not None and got[3] is not None and bound_word is not None and group is None and want_dz
+                and pair[6].get("dx_pl") and all(pair[6].get("needs", ()))):
+            pair_word = _h2_slot()
+        if pair_word is not None:
+            gs, bs = pair[3], pair[4]
+            sgs, sbs = _sink(gs), _sink(bs)
+            in_arena_s = sgs is not None and sbs is not None and sgs.is_contiguous() and sbs.is_contiguous()
+            sums_s = None if in_arena_s else torch.empty(2 * C, device=x.device, dtype=torch.float32)
+            call("tris_part_finalize_pair_f32", got[0].data_ptr(), got[3].data_ptr(), got[1], C, p_dz, p_dzx,
+                 P(sbs) if in_arena_s else P(sums_s), P(sgs) if in_arena_s else P(sums_s, C), P(gamma), P(invstd), P(gs), P(pair[2]),
+                 1.0 / float(count), math.sqrt(max(count - 1, 1)), dzw, bound_word, pair_word, _stream())
+        elif got is not None and bound_word is not None:
             call("tris_part_finalize_bound_f32", got[0].data_ptr(), got[1], C, p_dz, p_dzx, P(gamma), P(invstd), 1.0 / float(count),
                  math.sqrt(max(count - 1, 1)), dzw, bound_word, _stream())
         elif got is not None:
@@ -1945,6 +2026,14 @@ class BatchNormFn(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 dx = torch.empty_like(x)
                 apply(dy, None, None, None)
+        elif got is not None and pair_word is not None:
+            d_res = dy              # (what autograd routes to the shortcut BatchNorm's node; that node finds its work done)
+            dx, dxs = torch.empty_like(x), torch.empty_like(x)
+            call("tris_bn_bwd_apply_pair_pl_f32", P(dy), P(x), P(mean), P(invstd), P(gamma), p_dzx, P(pair[0]), P(pair[1]), P(pair[2]),
+                 P(gs), P(sgs) if in_arena_s else P(sums_s, C), p_dz, inv_cnt, P(dx), bound_word, P(dxs), pair_word, M, C, _stream())
+            pl_grad_out(dx, bound_word)
+            pl_grad_out(dxs, pair_word)
+            pair[6]["done"] = (dxs, in_arena_s, sums_s)
         elif got is not None:
             if want_dz:
                 d_res = dy          # the masked gradient IS the identity branch's gradient
@@ -1962,11 +2051,20 @@ class BatchNormFn(torch.autograd.Function):
             apply(dy, None if mask_x else y, d_res if want_dz else None, beta if mask_x else None)
         if ctx.grad_box is not None and d_res is not None and ctx.grad_box.deposit(d_res):
             d_res = None   # handed to the block's first conv
-        return dx, dg, db, None, None, d_res, None, None, None, None, None, None, None, None, None, None, None, None
+        return dx, dg, db, None, None, d_res, None, None, None, None, None, None, None, None, None, None, None, None, None
+
+
+def _bn_pair_write(pr):
+    """the fp32 output of a shortcut BatchNorm that was handed over as `_bn_pair`, for a bn3 that cannot take the pair after all"""
+    x, mean, invstd, gamma, beta = pr[:5]
+    y = torch.empty_like(x)
+    h2_mark_next(y)
+    call("tris_bn_apply_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), None, P(y), x.numel() // x.shape[-1], x.shape[-1], 0, _stream())
+    return y
 
 
 def batch_norm(x, gamma, beta, rmean, rvar, resid=None, relu=False, training=True, momentum=0.1, eps=1e-5, group=None,
-               grad_box=None, lazy=False, bwd_link=False, pool=False, planes=False, dx_planes=False):
+               grad_box=None, lazy=False, bwd_link=False, pool=False, planes=False, dx_planes=False, pair=False):
     """lazy=True (train-mode BatchNorm + ReLU whose ONLY consumer is ops.conv3x3, and conv3x3_bnin_ok said yes): the returned
     tensor is an unwritten buffer carrying `_bn_lazy`; pass it to ops.conv3x3 and nowhere else.
     planes / dx_planes (h2 with operand planes, train mode): the output / the input gradient is written as fp16 operand planes --
@@ -1977,9 +2075,9 @@ def batch_norm(x, gamma, beta, rmean, rvar, resid=None, relu=False, training=Tru
                      and x.shape[2] % 2 == 0 and cfg.bn_pool):
         # eval mode / shapes the fused op does not take: the two ops one after the other
         return avgpool2(BatchNormFn.apply(x, gamma, beta, rmean, rvar, resid, relu, training, momentum, eps, group, part, grad_box,
-                                          lazy, bwd_link, False, planes, dx_planes))
+                                          lazy, bwd_link, False, planes, dx_planes, pair))
     return BatchNormFn.apply(x, gamma, beta, rmean, rvar, resid, relu, training, momentum, eps, group, part, grad_box, lazy,
-                             bwd_link, pool, planes, dx_planes)
+                             bwd_link, pool, planes, dx_planes, pair)
 
 
 class AvgPool2Fn(torch.autograd.Function):
@@ -2003,11 +2101,22 @@ class AvgPool2Fn(torch.autograd.Function):
     def backward(ctx, dy):
         B, H, W, C = ctx.shape
         dy = unplanes(pl_grad_in(dy.contiguous()))
-        dx = torch.empty(B, H, W, C, device=dy.device, dtype=torch.float32)
-        call("tris_avgpool2_bwd_f32", P(dy), P(dx), B, H, W, C, _stream())
-        if ctx.grad_box_out is not None and ctx.grad_box_out.deposit(dx):
+        box = ctx.grad_box_out
+        if (box is not None and cfg.bn_pair and "pool" in cfg.bn_pair_parts and planes_on() and C % 4 == 0 and H % 2 == 0 and W % 2 == 0 and dy.data_ptr() % 16 == 0
+                and box.deposit(dy)):
+            box.pool = (H, W)     # the pooled gradient itself: the block's first conv reads it in place (GradBox.pool)
+            return None, None
+        dx = _avgpool2_bwd(dy, (B, H, W, C))
+        if box is not None and box.deposit(dx):
             dx = None
         return dx, None
+
+
+def _avgpool2_bwd(dy, shape):
+    B, H, W, C = shape
+    dx = torch.empty(B, H, W, C, device=dy.device, dtype=torch.float32)
+    call("tris_avgpool2_bwd_f32", P(dy), P(dx), B, H, W, C, _stream())
+    return dx
 
 
 def avgpool2(x, grad_box_out=None):
