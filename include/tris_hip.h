@@ -365,7 +365,8 @@ int tris_mha_bwd_f32(const float* qkv, const float* dout, float* dqkv, int N, in
                      void* stream);
 /* The same attention for ANY sequence length, flash-style on the f32 MFMA (no L x L matrix in memory): used for L > 64
  * (a ViT-B/16 trunk at 320 px has L = 401) and, where faster, for the short sequences too.  lse [N, heads, L] receives
- * the per-query log-sum-exp (saved for backward); delta [N, heads, L] is backward scratch (rowsum(dO * O)). */
+ * the per-query log-sum-exp (saved for backward); delta [N, heads, L] is backward scratch (rowsum(dO * O)).  qkv -- and in the
+ * backward out and dout -- are read with 16-byte loads: a pointer off that alignment is hipErrorInvalidValue, nothing is launched. */
 int tris_mha_mfma_fwd_f32(const float* qkv, float* out, float* lse, int N, int L, int W, int heads, int causal,
                           void* stream);
 int tris_mha_mfma_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse, float* delta,

@@ -309,7 +309,9 @@ extern "C" int tris_mha_mfma_fwd_f32(const float* qkv, float* out, float* lse, i
 extern "C" int tris_mha_mfma_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse,
                                      float* delta, float* dqkv, int N, int L, int W, int heads, int causal,
                                      void* stream) {
-  if (W != heads * HD || L < 1 || N < 1) return (int)hipErrorInvalidValue;
+  // (both launches read qkv, dout and out with 16-byte loads, as the forward reads qkv)
+  if (W != heads * HD || L < 1 || N < 1 || (((uintptr_t)qkv) & 15) || (((uintptr_t)dout) & 15) || (((uintptr_t)out) & 15))
+    return (int)hipErrorInvalidValue;
   const float scale = 1.0f / sqrtf((float)HD);
   const dim3 grid(cdiv(L, 64), heads, N);
   unsigned* amax = tris_internal_take_amax_next();   // (dqkv's amax word: both launches max into it)
