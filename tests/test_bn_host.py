@@ -211,3 +211,51 @@ def test_shapes_reach_the_paths_they_are_named_for():
         part, M = OB.partial_rows(rows, 4)
         assert part.shape == (rows, 2, 4) and M == rows * 128
     assert max(OB.FIN_ROWS) > 2048 > 513                      # both block sizes of the finalizers
+
+
+# ================================================================================================== hand-offs (tris_amd.ops, no launch)
+def test_carry_hands_over_the_riders_and_nothing_else():
+    from tris_amd import ops
+    assert set(ops.RIDERS) == {"_bn_link", "_bn_lazy", "_pl", "_h2"}
+    src, dst = torch.zeros(3), torch.zeros(3)
+    for k, name in enumerate(ops.RIDERS):
+        setattr(src, name, ("rider", k))
+    src._bn_part, src._act_link, src._other = ("part", 1), object(), 5
+    assert ops.carry(src, dst) is dst
+    assert {k: v for k, v in vars(dst).items()} == {name: ("rider", k) for k, name in enumerate(ops.RIDERS)}
+    bare = torch.zeros(3)
+    assert vars(ops.carry(torch.zeros(3), bare)) == {}          # a rider the source does not have is not set (to None) either
+
+
+def test_carry_refuses_the_stand_in_of_a_paired_shortcut():
+    from tris_amd import ops
+    src, dst = torch.zeros(1).expand(2, 3), torch.zeros(2, 3)
+    src._pl = ("tag",)
+    src._bn_pair = ops._BnPair(*(torch.zeros(3) for _ in range(5)), 1234, ops._BnPairState(True, (True, True, True)))
+    with pytest.raises(RuntimeError, match="bn3"):
+        ops.carry(src, dst)
+    assert vars(dst) == {}
+
+
+def test_bwd_link_is_taken_once_and_only_by_the_tensor_that_filled_it():
+    from tris_amd import ops
+    stat = [torch.zeros(4) for _ in range(5)]
+    dz, part, part2 = torch.ones(2, 4), torch.zeros(8, dtype=torch.float64), torch.ones(8, dtype=torch.float64)
+    link = ops._BnBwdLink(*stat, False)
+    assert link.take(dz) is None                                # never filled
+    link.fill(dz, part, 1, 77, part2)
+    got = link.take(dz)
+    assert isinstance(got, ops._BnTaken) and got._fields == ("part", "rows", "dzw", "part2")
+    assert got.part is part and got.rows == 1 and got.dzw == 77 and got.part2 is part2 and tuple(got) == (part, 1, 77, part2)
+    assert link.take(dz) is None                                # one use
+    link.fill(dz, part, 1)
+    got = link.take(dz)
+    assert got.dzw is None and got.part2 is None
+    link.fill(dz, part, 1)
+    dz.add_(1.0)                                                # autograd accumulated a second consumer's gradient into it
+    assert link.take(dz) is None
+    link.fill(dz, part, 1)
+    assert link.take(dz.clone()) is None                        # another tensor arrives
+    assert link.take(dz) is None                                # ... and that use emptied the link
+    link.fill(dz, part, 1)
+    assert link.take(dz.view(4, 2)) is None                     # the same storage under another shape

@@ -14,6 +14,7 @@ see tris_amd.optim).  Backward kernels then write the weight gradient straight i
 """
 import math
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -592,13 +593,50 @@ def nchw_to_nhwc(x):
 # A conv forward can emit the BatchNorm batch statistics of its output from the GEMM epilogue (tris_*_bnstat_f32).
 # The fp64 partials travel from the conv Function to the BatchNorm Function as an attribute of the output tensor
 # (`y._bn_part`, set inside the Function's forward: the object returned by apply() is that same tensor).
+# The other records between the autograd nodes of the BatchNorm family (field order as the tests index them): `y._bn_lazy`, `y._bn_pair`
+# (ops.batch_norm: y is unwritten, its one consumer normalises x itself; bound / word: amax word of an upper bound of the would-be
+# contents, bound None outside h2; state: what the pair's two backward nodes talk through) and what _BnBwdLink.take() returns (the
+# product's partial rows of the two sums, the amax word of the masked gradient, cfg.bn_pair: the rows of the shortcut's third sum)
+_BN = [(f, torch.Tensor) for f in ("x", "mean", "invstd", "gamma", "beta")]   # (a BatchNorm: its input, statistics and parameters)
+_BnPart = NamedTuple("_BnPart", [("part", torch.Tensor), ("rows", int)])
+_BnLazy = NamedTuple("_BnLazy", _BN + [("bound", Optional[int])])
+_BnPair = NamedTuple("_BnPair", _BN + [("word", int), ("state", object)])
+_BnTaken = NamedTuple("_BnTaken", [("part", torch.Tensor), ("rows", int), ("dzw", Optional[int]), ("part2", Optional[torch.Tensor])])
+
+
+class _BnPairState:
+    """dx_pl, needs: what bn3's backward needs to know of its shortcut BatchNorm's (dx goes out as planes; needs_input_grad of x, gamma,
+    beta); done = (dxs, in_arena_s, sums_s): where it leaves dx and the sums it formed for it"""
+    __slots__ = ("dx_pl", "needs", "done")
+
+    def __init__(self, dx_pl, needs):
+        self.dx_pl, self.needs, self.done = dx_pl, needs, None
+
+
+# What rides on a tensor across an autograd node that is an identity (SegmentedStep.cut, GradReducer.boundary): the hand-offs to the
+# tensor's consumer and its plane / amax tags.  (`_bn_part` is read by the very next op; `_bn_pair` must not pass: carry)
+RIDERS = ("_bn_link", "_bn_lazy", "_pl", "_h2")
+
+
+def carry(src, dst):
+    """dst is src behind an identity node: hand over what rides on src.  -> dst  (Not a `_bn_pair` stand-in: it holds no data, whoever
+    reads dst without the hand-over reads garbage, and only a BatchNorm takes it.)"""
+    if getattr(src, "_bn_pair", None) is not None:
+        raise RuntimeError("the unwritten output of a paired shortcut BatchNorm goes to the block's bn3 and nowhere else")
+    for attr in RIDERS:
+        v = getattr(src, attr, None)
+        if v is not None:
+            setattr(dst, attr, v)
+    return dst
+
+
 def _launch_with_stats(y, M, N, launch):
     import ctypes
     part = torch.empty(((M + 127) // 128) * 2 * N, device=y.device, dtype=torch.float64)
     rows = ctypes.c_int(0)
     launch(part, ctypes.byref(rows))
     if rows.value > 0:
-        y._bn_part = (part, rows.value)
+        y._bn_part = _BnPart(part, rows.value)
 
 
 def _declinable(name, *args):
@@ -934,16 +972,6 @@ def h2_mark_next(t):
     t._h2 = (_H2["step"], slot, t._version)
 
 
-def h2_bound_word(gamma, beta, C, xhat_max):
-    """amax word holding an upper bound of |relu(bn(x))| for a train-mode BatchNorm whose output is never written (None: not h2)"""
-    if not h2_on():
-        return None
-    slot = _h2_slot()
-    if slot is not None:
-        call("tris_bn_out_bound_f32", P(gamma), P(beta), C, float(xhat_max), slot, _stream())
-    return slot
-
-
 def _h2_tag_slot(t):
     tag = getattr(t, "_h2", None)
     if tag is not None and tag[0] == _H2["step"] and tag[2] == t._version:
@@ -1249,7 +1277,7 @@ class _BnBwdLink:
         self.part2 = part2
 
     def take(self, dy):
-        """(part, rows) if dy IS the masked gradient this link's product left (same storage, version and shape); None if no product
+        """_BnTaken if dy IS the masked gradient this link's product left (same storage, version and shape); None if no product
         filled the link -- or if what arrives is something else: a second consumer's gradient was added to it by autograd (a
         down-sampling block whose shortcut backward ran late, a model that uses the BatchNorm output twice).  The caller then runs
         the usual two passes on whatever arrived, which is correct for any sum of gradients (the ReLU mask is idempotent: masking
@@ -1258,11 +1286,7 @@ class _BnBwdLink:
         self.dz = self.part = self.dzw = self.part2 = None
         if dz is None or (dy.data_ptr(), dy._version, tuple(dy.shape)) != dz:
             return None
-        return part, rows, dzw, part2
-
-
-def _bn_bwd_fuse_enabled():
-    return cfg.bn_bwd_fuse
+        return _BnTaken(part, rows, dzw, part2)
 
 
 class LinearFn(torch.autograd.Function):
@@ -1361,7 +1385,7 @@ class LinearFn(torch.autograd.Function):
                         if pool is not None:
                             call("tris_gemm_resid_pool_next", pool[0], pool[1])
                         if part2 is not None:
-                            call("tris_gemm_bnbwd_x2_next", P(pr2[0]), P(pr2[1]), P(pr2[2]), part2.data_ptr())
+                            call("tris_gemm_bnbwd_x2_next", P(pr2.x), P(pr2.mean), P(pr2.invstd), part2.data_ptr())
                         call("tris_gemm_bnbwd_f32", pp[0], pp[1], P(dx), M, K, N, P(extra), K, P(link.x), by,
                              P(link.mean), P(link.invstd), P(link.gamma), P(link.beta), part.data_ptr(), ctypes.byref(rows), _stream())
                         return rows.value > 0     # (False: the entry point declined the shape, nothing was launched)
@@ -1403,7 +1427,7 @@ def linear(x, w, b=None, resid=None, act=0, stats=False, grad_box=None, grad_box
     """act_link=True: x is the output of linear_qgelu and THIS product is its only consumer -- the QuickGELU backward rides this
     product's data-gradient epilogue (the caller vouches for the single consumer)"""
     link = getattr(x, "_bn_link", None)
-    if link is not None and not (torch.is_grad_enabled() and x.requires_grad and _bn_bwd_fuse_enabled()):
+    if link is not None and not (torch.is_grad_enabled() and x.requires_grad and cfg.bn_bwd_fuse):
         link = None
     alink = getattr(x, "_act_link", None) if (act_link and torch.is_grad_enabled() and x.requires_grad) else None
     return LinearFn.apply(x, w, b, resid, act, stats, grad_box, grad_box_out, grad_box_res, link, alink)
@@ -1564,7 +1588,7 @@ class Conv3x3Fn(torch.autograd.Function):
     def forward(ctx, x, w, stride, stats=False, lazy=None, bn_link=None):
         """bn_link: x is the output of a BatchNorm + ReLU with no other consumer (_BnBwdLink): the data gradient reduces that
         BatchNorm's backward sums in its epilogue.
-        lazy = (x_raw, mean, invstd, gamma, beta): `x` is the NOT-YET-WRITTEN output buffer of a BatchNorm + ReLU over x_raw
+        lazy (_BnLazy): `x` is the NOT-YET-WRITTEN output buffer of a BatchNorm + ReLU over lazy.x
         (batch_norm(..., lazy=True)); the direct kernels normalise x_raw while they stage it and `x` is never written -- or, when
         they cannot serve the shape after all, it is written here first and everything proceeds as usual.  (h2: the unwritten
         buffer carries the amax word of an upper bound of its would-be contents, BatchNormFn.forward.)"""
@@ -1579,27 +1603,25 @@ class Conv3x3Fn(torch.autograd.Function):
         ctx.lazy = None
         ctx.stride = stride
         if lazy is not None:
-            xr, mean, invstd, gamma, beta, bound = lazy
             if stride == 1 and conv3x3_bnin_ok(x.shape, Cout):
                 y = torch.empty(B, H, W, Cout, device=x.device, dtype=torch.float32)
                 fl = 2.0 * B * H * W * Cout * 9 * Cin
                 nb = 4.0 * (B * H * W * (Cin + Cout) + 9 * Cin * Cout)
-                ctx.h2_in = bound      # (None outside h2)
+                ctx.h2_in = bound = lazy.bound      # (None outside h2)
 
                 def launch(part, rows):
                     return _timed("conv3x3_fwd", fl, lambda: (bound is not None and h2_arm(None, ctx.params[0], a_slot=bound), call(
-                        "tris_conv3x3_fwd_bnin_f32", P(xr), P(mean), P(invstd), P(gamma), P(beta), P(w), P(y), B, H, W, Cin, Cout,
-                        None if part is None else part.data_ptr(), rows, _stream()))[1], nbytes=nb,
+                        "tris_conv3x3_fwd_bnin_f32", P(lazy.x), P(lazy.mean), P(lazy.invstd), P(lazy.gamma), P(lazy.beta), P(w), P(y),
+                        B, H, W, Cin, Cout, None if part is None else part.data_ptr(), rows, _stream()))[1], nbytes=nb,
                         tag=_shape_tag(f"bnin B{B} {H}x{W} {Cin}->{Cout}"))
                 if stats:
                     _launch_with_stats(y, B * H * W, Cout, launch)
                 else:
                     launch(None, None)
                 ctx.lazy = True
-                ctx.save_for_backward(xr, w, mean, invstd, gamma, beta)
+                ctx.save_for_backward(lazy.x, w, lazy.mean, lazy.invstd, lazy.gamma, lazy.beta)
                 return y
-            h2_mark_next(x)
-            call("tris_bn_apply_f32", P(xr), P(mean), P(invstd), P(gamma), P(beta), None, P(x), B * H * W, Cin, 1, _stream())
+            _bn_write(lazy.x, lazy.mean, lazy.invstd, lazy.gamma, lazy.beta, x, True)
         if pl_word(x) is not None and (Cin % 32 != 0 or stride != 1):
             x = unplanes(x)        # (the fast kernels' gather needs 32-channel pieces; the stem's strided first convolution reads the image)
         ctx.x_pl = getattr(x, "_pl", None)
@@ -1674,9 +1696,7 @@ class Conv3x3Fn(torch.autograd.Function):
                     return _timed("conv3x3_wgrad", fl, lambda: (ctx.h2_in is not None and h2_arm(dy, None, b_slot=ctx.h2_in), call(
                         "tris_conv3x3_wgrad_bnin_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(dy), P(o), B, H, W, Cin,
                         Cout, P(ws), ws.numel() * 4, _stream()))[1], nbytes=nb, tag=_shape_tag(f"bnin B{B} {H}x{W} {Cin}->{Cout}"))
-                xin = torch.empty_like(x)   # materialise relu(bn(x)) after all
-                h2_mark_next(xin)
-                call("tris_bn_apply_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), None, P(xin), B * H * W, Cin, 1, _stream())
+                xin = _bn_write(x, mean, invstd, gamma, beta, torch.empty_like(x), True)   # materialise relu(bn(x)) after all
             return _timed("conv3x3_wgrad", fl, lambda: (lambda pp: call(
                 "tris_conv3x3_wgrad_f32", pp[1], pp[0], P(o), B, H, W, Cin, Cout, ctx.stride, P(ws), ws.numel() * 4, _stream()))(
                     h2_pp(dy, xin, k_red=dy.shape[0] * dy.shape[1] * dy.shape[2])), nbytes=nb,
@@ -1707,12 +1727,182 @@ def conv3x3_bnin_ok(xshape, Cout):
 
 def conv3x3(x, w, stride=1, stats=False):
     link = getattr(x, "_bn_link", None)
-    if link is not None and not (torch.is_grad_enabled() and x.requires_grad and _bn_bwd_fuse_enabled()):
+    if link is not None and not (torch.is_grad_enabled() and x.requires_grad and cfg.bn_bwd_fuse):
         link = None
     return Conv3x3Fn.apply(x, w, stride, stats, getattr(x, "_bn_lazy", None), link)
 
 
 # ----------------------------------------------------------------------------------------------- BatchNorm
+# _BnOpts: what ops.batch_norm tells BatchNormFn beyond the tensors autograd must see (one argument of apply; ops.batch_norm).
+_BnOpts = NamedTuple("_BnOpts", [("relu", bool), ("training", bool), ("momentum", float), ("eps", float), ("group", object),
+                                 ("part", Optional[_BnPart]), ("grad_box", object), ("lazy", bool), ("bwd_link", bool), ("pool", bool),
+                                 ("planes", bool), ("dx_planes", bool), ("pair", bool)])
+# _BnPlan: what BatchNormFn.forward decides -- from its options, the shapes, cfg and planes_on() -- before it launches anything.
+# use_pl / dx_pl: the output is written as operand planes / the input gradient will be; pair_out: the output is not written, what
+# comes back is the stand-in carrying `_bn_pair`; pair_in (bn3 of that block): the residual is such a stand-in and this pass normalises
+# the shortcut itself; lazy: y stays UNWRITTEN -- its only consumer (a 3x3 convolution with direct kernels) normalises x while staging it
+_BnPlan = NamedTuple("_BnPlan", [("use_pl", bool), ("dx_pl", bool), ("pair_out", bool), ("pair_in", Optional[_BnPair]), ("lazy", bool)])
+_Bn = NamedTuple("_Bn", _BN)
+# _BnBwd: the BatchNorm one backward pass works on and the constants of that pass (x is [M, C]; pool: the forward was BatchNorm + ReLU +
+# AvgPool2d(2), dy is the POOLED gradient; xmax = sqrt(count - 1), Samuelson's bound of |xhat|)
+_BnBwd = NamedTuple("_BnBwd", _BN + [("M", int), ("C", int), ("pool", bool), ("inv_cnt", float), ("xmax", float)])
+
+
+def _bn_plan(o, x, resid):
+    C = x.shape[-1]
+    fits = bool(o.training and C % 8 == 0 and 2048 % C == 0 and planes_on())
+    use_pl = bool(o.planes and fits)
+    lazy = o.lazy and not use_pl
+    pair_out = bool(o.pair and cfg.bn_pair and "fwd" in cfg.bn_pair_parts and fits and o.group is None and resid is None and not o.relu
+                    and not o.pool and not lazy and not use_pl)
+    pr = getattr(resid, "_bn_pair", None) if resid is not None else None
+    take = pr is not None and use_pl and o.group is None and o.relu and not o.pool and pr.x.shape == x.shape
+    return _BnPlan(use_pl, bool(o.dx_planes and fits), pair_out, pr if take else None, bool(lazy and o.training and o.relu and resid is None))
+
+
+def _bn_bound_words(resid, pr):
+    """-> (w, rw): a fresh amax word for the bound of a plane output, and the word of the residual it is added to -- its plane word,
+    the bound of a paired shortcut, else its amax (a by-product or a pre-pass); (None, None) where either is not to be had"""
+    w, rw = _h2_slot(), None
+    if pr is not None:
+        rw = pr.word
+    elif resid is not None:
+        rw = pl_word(resid)
+        rw = _h2_amax(resid) if rw is None else rw
+    return (w, rw) if w is not None and (resid is None or rw is not None) else (None, None)
+
+
+def _bn_local_stats(x, part, eps, momentum, dst, rm, rv, bound=None):
+    """this rank's statistics of x into dst, running statistics rm / rv updated (None: not here): finalized from the partial sums out of
+    the producing conv's epilogue -- bound = (gamma, beta, xmax, resid word, word): that launch also leaves the bound of the plane
+    output in `word` -- or by a statistics pass"""
+    M, C = x.numel() // x.shape[-1], x.shape[-1]
+    if part is not None and bound is not None:
+        gamma, beta, xmax, rw, w = bound
+        call("tris_bn_finalize_bound_f32", part.part.data_ptr(), part.rows, M, C, eps, momentum, P(dst), P(rm), P(rv), P(gamma), P(beta),
+             xmax, rw, w, _stream())
+    elif part is not None:
+        call("tris_bn_finalize_f32", part.part.data_ptr(), part.rows, M, C, eps, momentum, P(dst), P(rm), P(rv), _stream())
+    else:
+        ws = workspace(query("tris_col_workspace_bytes", M, C))
+        call("tris_bn_stats_f32", P(x), M, C, eps, momentum, P(dst), P(rm), P(rv), P(ws), _stream())
+
+
+def _bn_statistics(o, plan, x, stats, gamma, beta, rmean, rvar, resid, world, xmax):
+    """train mode: local statistics, or combined over the `world` ranks of o.group through the SyncBN mailbox or a c10d gather.
+    -> (word, rw): the plane output's bound word and its residual's word where the finalizing launch formed the bound too"""
+    M, C = x.numel() // x.shape[-1], x.shape[-1]
+    word = rw = None
+    if o.group is None:
+        if o.part is not None and (plan.use_pl or plan.pair_out):
+            # partial sums from the producing conv's epilogue; the same launch leaves the bound of the plane output
+            # (pair_out: the bound of the shortcut's value, which bn3's launch chains into its own as add_word)
+            word, rw = _bn_bound_words(resid, plan.pair_in)
+        _bn_local_stats(x, o.part, o.eps, o.momentum, stats, rmean, rvar, None if word is None else (gamma, beta, xmax, rw, word))
+        return word, rw
+    from . import comm
+    mb = comm.syncbn_mailbox(o.group, 3 * C)
+    if mb is not None:   # one launch: peer-mailbox exchange + combine (+ running statistics)
+        loc = torch.empty(3 * C, device=x.device, dtype=torch.float32)
+        _bn_local_stats(x, o.part, o.eps, o.momentum, loc, None, None)
+        if plan.use_pl and cfg.syncbn_bound:   # ... + the bound word of the plane output (what tris_bn_out_bound2_f32 would launch for)
+            word, rw = _bn_bound_words(resid, plan.pair_in)
+        if word is not None:
+            mb.bn_combine_bound(loc, C, M, o.eps, o.momentum, stats, rmean, rvar, gamma, beta, xmax, rw, word)
+        else:
+            mb.bn_combine(loc, C, M, o.eps, o.momentum, stats, rmean, rvar)
+    else:
+        _bn_local_stats(x, o.part, o.eps, o.momentum, stats, None, None)
+        allv = torch.empty(world * 3 * C, device=x.device, dtype=torch.float32)
+        comm.syncbn_all_gather_into(allv, stats, group=o.group)   # the stats block travels as is
+        call("tris_bn_sync_combine_f32", P(allv), world, C, M, o.eps, o.momentum, P(stats), P(rmean), P(rvar), _stream())
+    return word, rw
+
+
+def _bn_write(x, mean, invstd, gamma, beta, y, relu, resid=None):
+    """the plain apply pass: y = relu?(bn(x) + resid?) written in fp32, its amax a by-product of the launch.  -> y"""
+    h2_mark_next(y)
+    call("tris_bn_apply_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(resid), P(y), x.numel() // x.shape[-1], x.shape[-1],
+         int(relu), _stream())
+    return y
+
+
+def _bn_apply(o, plan, bn, resid, y, word, rw):
+    """the apply pass in the forms that write y: operand planes under the bound `word` (+ pool, + the paired shortcut), fp32 (+ pool);
+    lazy: none.  -> the ReLU mask bytes of a plane output whose consumer will mask with them"""
+    x, pr, y_mask, p = bn.x, plan.pair_in, None, [P(t) for t in bn]
+    M, C = x.numel() // x.shape[-1], x.shape[-1]
+    if plan.use_pl and o.pool:
+        call("tris_bn_apply_pool_pl_f32", *p, P(y), word, x.shape[0], x.shape[1], x.shape[2], C, _stream())
+    elif plan.use_pl:
+        if cfg.bn_bitmask and o.bwd_link and o.relu and resid is not None:
+            # out = relu(bn(x) + identity) with ONE consumer whose data-gradient epilogue will mask with it (_BnBwdLink.from_y):
+            # the pass also leaves the mask as one byte per 8 channels, so that epilogue reads a bit, not the plane element
+            y_mask = torch.empty(M * C // 8, device=x.device, dtype=torch.uint8)
+            call("tris_bn_mask_next", y_mask.data_ptr())
+        if pr is not None:   # relu(bn3(x) + bn_s(xs)): the shortcut's BatchNorm in the same pass
+            call("tris_bn_apply_pair_pl_f32", *p, P(pr.x), P(pr.mean), P(pr.invstd), P(pr.gamma), P(pr.beta), P(y), word, M, C, _stream())
+        else:
+            rk = 0 if resid is None else (2 if pl_word(resid) is not None else 1)
+            call("tris_bn_apply_pl_f32", *p, P(resid), rk, rw if rk == 2 else None, P(y), word, M, C, int(o.relu), _stream())
+    elif o.pool:
+        h2_mark_next(y)
+        call("tris_bn_apply_pool_f32", *p, P(y), x.shape[0], x.shape[1], x.shape[2], C, _stream())
+    elif not plan.lazy:
+        _bn_write(*bn, y, o.relu, resid)
+    if plan.use_pl:
+        pl_tag(y, word)
+    return y_mask
+
+
+def _bn_bwd_reduce(b, dy, y, mask_x, p_dz, p_dzx, dzw, dz_out):
+    """sum(dz), sum(dz * xhat) in a pass of their own over dy (no product left them behind; pooled: the mask from x); dz_out: the
+    pass also writes the masked gradient dz there"""
+    ws, px = workspace(query("tris_col_workspace_bytes", b.M, b.C)), (P(b.x), P(b.mean), P(b.invstd))
+    if dzw is not None:
+        call("tris_amax_next", dzw)
+    if b.pool:
+        call("tris_bn_bwd_reduce_pool_f32", P(dy), *px, *b.x.shape[:3], b.C, p_dz, p_dzx, P(ws), P(b.gamma), P(b.beta), _stream())
+    elif pl_word(y) is not None and not mask_x:
+        call("tris_bn_bwd_reduce_pl_f32", P(dy), P(y), *px, b.M, b.C, p_dz, p_dzx, P(ws), P(dz_out), _stream())
+    else:
+        call("tris_bn_bwd_reduce_f32", P(dy), None if mask_x else P(y), *px, b.M, b.C, p_dz, p_dzx, P(ws),
+             P(b.gamma) if mask_x else None, P(b.beta) if mask_x else None, P(dz_out), _stream())
+
+
+def _bn_bwd_apply(b, g, ymask, dz_out, beta_m, dx, p_dz, p_dzx, dzw, word, dx_pl):
+    """dx from the (masked or to-be-masked) gradient g; dx_pl: as operand planes, where the convolution before takes them, under the
+    bound `word` (None: no finalizer has formed it, a launch of its own does)"""
+    px = (P(b.x), P(b.mean), P(b.invstd), P(b.gamma))
+    if dx_pl:
+        if word is None:
+            word = _h2_slot()
+            call("tris_bn_bwd_bound_f32", P(b.gamma), P(b.invstd), p_dz, p_dzx, b.C, b.inv_cnt, b.xmax, dzw, word, _stream())
+        if b.pool:
+            call("tris_bn_bwd_apply_pool_pl_f32", P(g), *px, P(b.beta), p_dz, p_dzx, b.inv_cnt, P(dx), word, *b.x.shape[:3], b.C, _stream())
+        else:
+            if ymask is not None and pl_word(ymask) is None:
+                raise RuntimeError("operand planes: the ReLU mask of a plane-output BatchNorm must come from plane y")
+            call("tris_bn_bwd_apply_pl_f32", P(g), P(ymask), *px, p_dz, p_dzx, b.inv_cnt, P(dx), word, P(dz_out), b.M, b.C, P(beta_m),
+                 _stream())
+        pl_grad_out(dx, word)
+        return
+    h2_mark_next(dx)
+    if b.pool:
+        call("tris_bn_bwd_apply_pool_f32", P(g), *px, P(b.beta), p_dz, p_dzx, b.inv_cnt, P(dx), *b.x.shape[:3], b.C, _stream())
+    else:
+        call("tris_bn_bwd_apply_f32", P(g), P(unplanes(ymask)) if ymask is not None else None, *px, p_dz, p_dzx, b.inv_cnt, P(dx),
+             P(dz_out), b.M, b.C, P(beta_m), _stream())
+
+
+def _bn_param_grads(ctx, sums, C):
+    """(dgamma, dbeta) out of the two sums (sum(dz), sum(dz * xhat)) of a backward that did not write them into the arena"""
+    return (_emit(ctx.params[0], lambda o: o.copy_(sums[C:]), ctx.needs_input_grad[1]),
+            _emit(ctx.params[1], lambda o: o.copy_(sums[:C]), ctx.needs_input_grad[2]))
+
+
+
+
 class BatchNormFn(torch.autograd.Function):
     """BatchNorm2d on channels-last x [..., C] with optional fused residual add and ReLU.
 
@@ -1720,201 +1910,103 @@ class BatchNormFn(torch.autograd.Function):
     SyncBatchNorm).  training=False: running statistics (forward only)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, rmean, rvar, resid, relu, training, momentum, eps, group, part=None, grad_box=None,
-                lazy=False, bwd_link=False, pool=False, planes=False, dx_planes=False, pair=False):
-        """planes: the output is WRITTEN as fp16 operand planes (every consumer is a product, a plane-aware BatchNorm / pool, or goes
-        through ops.unplanes); dx_planes: so is the input gradient (its one consumer is the backward of the convolution before).
-        pair (the shortcut BatchNorm of a down-sampling Bottleneck; cfg.bn_pair): the output's ONLY reader is the block's bn3, as its
-        residual -- where the plane path applies the statistics are formed here, the output is NOT written, and what comes back is an
-        unallocated stand-in carrying `_bn_pair`; bn3's pass normalises the shortcut's raw input itself (tris_bn_apply_pair_pl_f32)"""
+    def forward(ctx, x, gamma, beta, rmean, rvar, resid, o):
+        """o: _BnOpts.  The steps: plan (_bn_plan), statistics (_bn_statistics), apply (_bn_apply), hand-offs"""
         _chk(x, gamma, beta, rmean, rvar, resid)
-        y_mask = None
         x = x.contiguous()
         C = x.shape[-1]
         M = x.numel() // C
-        use_pl = bool(planes and training and C % 8 == 0 and 2048 % C == 0 and planes_on())
-        ctx.dx_pl = bool(dx_planes and training and C % 8 == 0 and 2048 % C == 0 and planes_on())
-        if use_pl:
-            lazy = False
-        pair_out = bool(pair and cfg.bn_pair and "fwd" in cfg.bn_pair_parts and training and group is None and resid is None and not relu
-                        and not pool and not lazy and not use_pl and C % 8 == 0 and 2048 % C == 0 and planes_on())
-        pr = getattr(resid, "_bn_pair", None) if resid is not None else None     # (bn3 of that block: the shortcut to normalise)
-        if pr is not None and not (use_pl and group is None and relu and not pool and pr[0].shape == x.shape):
-            resid, pr = _bn_pair_write(pr), None     # (this BatchNorm cannot take the pair: the shortcut's output as it used to be)
-        # pool: the output is avgpool2(relu(bn(x))) -- BatchNorm + ReLU + AvgPool2d(2) as one op, the full-size tensor never written
-        pool = bool(pool)   # (ops.batch_norm has checked: train mode, ReLU, no residual, even map)
-        y = (torch.empty(x.shape[0], x.shape[1] // 2, x.shape[2] // 2, C, device=x.device, dtype=torch.float32) if pool
+        plan = _bn_plan(o, x, resid)
+        use_pl, pair_out, pr = plan.use_pl, plan.pair_out, plan.pair_in
+        if pr is None and getattr(resid, "_bn_pair", None) is not None:
+            # (this BatchNorm cannot take the pair: the shortcut's fp32 output is written first, as it used to be)
+            q = resid._bn_pair
+            resid = _bn_write(q.x, q.mean, q.invstd, q.gamma, q.beta, torch.empty_like(q.x), False)
+        y = (torch.empty(x.shape[0], x.shape[1] // 2, x.shape[2] // 2, C, device=x.device, dtype=torch.float32) if o.pool
              else (None if pair_out else torch.empty_like(x)))
         if resid is not None and pr is None:
             resid = resid.contiguous()
-
-        def resid_word():
-            """amax word of the residual: its plane word, the bound of a paired shortcut, else its amax (a by-product or a pre-pass)"""
-            if pr is not None:
-                return pr[5]
-            w = pl_word(resid)
-            return w if w is not None else _h2_amax(resid)
-        count = M
-        if training:
+        world = 1
+        if o.training and o.group is not None:
+            from . import comm
+            world = comm.world_size(o.group)
+        count = M * world  # DistributedSampler gives every rank the same per-step batch
+        xmax = math.sqrt(max(count - 1, 1))   # (Samuelson: |xhat| <= sqrt(n - 1) -- what every bound of normalised values starts from)
+        word = rw = None   # (operand planes: the output's bound word and its residual's, formed by the finalizer where it can)
+        if o.training:
             stats = torch.empty(3 * C, device=x.device, dtype=torch.float32)
-
-            pl_bound = {"word": None, "resid": None}   # (operand planes: the output's bound word, formed by the finalizer where it can)
-
-            def local_stats(rm, rv, dst=None):
-                dst = stats if dst is None else dst
-                if part is not None and (use_pl or pair_out) and group is None:
-                    # partial sums from the producing conv's epilogue; the same launch leaves the bound of the plane output
-                    # (pair_out: the bound of the shortcut's value, which bn3's launch chains into its own as add_word)
-                    w_, rw_ = _h2_slot(), None
-                    if resid is not None:
-                        rw_ = resid_word()
-                    if w_ is not None and (resid is None or rw_ is not None):
-                        call("tris_bn_finalize_bound_f32", part[0].data_ptr(), part[1], M, C, eps, momentum, P(dst), P(rm), P(rv),
-                             P(gamma), P(beta), math.sqrt(max(M - 1, 1)), rw_, w_, _stream())
-                        pl_bound["word"], pl_bound["resid"] = w_, rw_
-                        return
-                if part is not None:  # partial sums came out of the producing conv's epilogue
-                    call("tris_bn_finalize_f32", part[0].data_ptr(), part[1], M, C, eps, momentum, P(dst), P(rm),
-                         P(rv), _stream())
-                else:
-                    ws = workspace(query("tris_col_workspace_bytes", M, C))
-                    call("tris_bn_stats_f32", P(x), M, C, eps, momentum, P(dst), P(rm), P(rv), P(ws), _stream())
-            if group is None:
-                local_stats(rmean, rvar)
-            else:
-                from . import comm
-                world = comm.world_size(group)
-                mb = comm.syncbn_mailbox(group, 3 * C)
-                if mb is not None:   # one launch: peer-mailbox exchange + combine (+ running statistics)
-                    loc = torch.empty(3 * C, device=x.device, dtype=torch.float32)
-                    local_stats(None, None, dst=loc)
-                    w_ = rw_ = None
-                    if use_pl and cfg.syncbn_bound:   # ... + the bound word of the plane output (what tris_bn_out_bound2_f32 would launch for)
-                        w_ = _h2_slot()
-                        if resid is not None:
-                            rw_ = resid_word()
-                    if w_ is not None and (resid is None or rw_ is not None):
-                        mb.bn_combine_bound(loc, C, M, eps, momentum, stats, rmean, rvar, gamma, beta,
-                                            math.sqrt(max(M * world - 1, 1)), rw_, w_)
-                        pl_bound["word"], pl_bound["resid"] = w_, rw_
-                    else:
-                        mb.bn_combine(loc, C, M, eps, momentum, stats, rmean, rvar)
-                else:
-                    local_stats(None, None)
-                    allv = torch.empty(world * 3 * C, device=x.device, dtype=torch.float32)
-                    comm.syncbn_all_gather_into(allv, stats, group=group)   # the stats block travels as is
-                    call("tris_bn_sync_combine_f32", P(allv), world, C, M, eps, momentum, P(stats), P(rmean), P(rvar),
-                         _stream())
-                count = M * world  # DistributedSampler gives every rank the same per-step batch
-            mean, invstd = stats[:C], stats[C:2 * C]
+            word, rw = _bn_statistics(o, plan, x, stats, gamma, beta, rmean, rvar, resid, world, xmax)
+            bn = _Bn(x, stats[:C], stats[C:2 * C], gamma, beta)
         else:
-            mean = rmean
-            invstd = torch.rsqrt(rvar + eps)
-        # lazy: y stays UNWRITTEN -- its only consumer (a 3x3 convolution with direct kernels) normalises x while staging it
-        lazy = bool(lazy and training and relu and resid is None)
+            bn = _Bn(x, rmean, torch.rsqrt(rvar + o.eps), gamma, beta)
         if not use_pl and resid is not None:
             resid = unplanes(resid)
-        if pair_out and pl_bound["word"] is None:
-            # (statistics from a pass of their own -- a convolution too small for the fused epilogue: the bound in a launch of its own)
-            pl_bound["word"] = _h2_slot()
-            if pl_bound["word"] is not None:
-                call("tris_bn_out_bound2_f32", P(gamma), P(beta), C, math.sqrt(max(count - 1, 1)), None, pl_bound["word"], _stream())
+        if (use_pl or pair_out) and word is None:
+            # the scale must exist before the pass writes: Samuelson's bound of the normalised values from the affine parameters,
+            # plus the bound (or amax) of the residual it is added to -- in a launch of its own where no finalizer formed it
+            # (pair_out: statistics from a pass of their own, a convolution too small for the fused epilogue)
+            word, rw = _bn_bound_words(resid, pr)
+            if word is not None:
+                call("tris_bn_out_bound2_f32", P(gamma), P(beta), C, xmax, rw, word, _stream())
+            elif use_pl:
+                raise RuntimeError("operand planes: no amax word for a BatchNorm output / its residual")
             else:                                      # (no amax word left in the pool: the shortcut is written after all)
                 pair_out, y = False, torch.empty_like(x)
+        ctx.pair_state = y_mask = None
         if pair_out:
             # neither allocated nor written: autograd needs a tensor of the output's shape to route bn3's residual gradient back here
             y = torch.empty(1, device=x.device, dtype=torch.float32).expand(x.shape)
-            # (the dict: what bn3's backward needs to know of this BatchNorm's, and where it leaves dx and the sums it formed for it)
-            ctx.pair_state = {"dx_pl": ctx.dx_pl, "needs": tuple(ctx.needs_input_grad[:3])}
-            y._bn_pair = (x, mean, invstd, gamma, beta, pl_bound["word"], ctx.pair_state)
-        elif use_pl:
-            # the scale must exist before the pass writes: Samuelson's bound of the normalised values from the affine parameters,
-            # plus the bound (or amax) of the residual it is added to
-            rk = 0 if resid is None else (2 if pl_word(resid) is not None else 1)
-            word = pl_bound["word"] if training else None
-            rw = pl_bound["resid"] if word is not None else None
-            if word is None:
-                word = _h2_slot()
-                if resid is not None:
-                    rw = resid_word()
-                if word is None or (resid is not None and rw is None):
-                    raise RuntimeError("operand planes: no amax word for a BatchNorm output / its residual")
-                call("tris_bn_out_bound2_f32", P(gamma), P(beta), C, math.sqrt(max(count - 1, 1)), rw, word, _stream())
-            if pool:
-                call("tris_bn_apply_pool_pl_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(y), word, x.shape[0], x.shape[1],
-                     x.shape[2], C, _stream())
-            else:
-                if cfg.bn_bitmask and training and bwd_link and relu and resid is not None:
-                    # out = relu(bn(x) + identity) with ONE consumer whose data-gradient epilogue will mask with it (_BnBwdLink.from_y):
-                    # the pass also leaves the mask as one byte per 8 channels, so that epilogue reads a bit, not the plane element
-                    y_mask = torch.empty(M * C // 8, device=x.device, dtype=torch.uint8)
-                    call("tris_bn_mask_next", y_mask.data_ptr())
-                if pr is not None:   # relu(bn3(x) + bn_s(xs)): the shortcut's BatchNorm in the same pass
-                    call("tris_bn_apply_pair_pl_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(pr[0]), P(pr[1]), P(pr[2]), P(pr[3]),
-                         P(pr[4]), P(y), word, M, C, _stream())
-                else:
-                    call("tris_bn_apply_pl_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(resid), rk, rw if rk == 2 else None,
-                         P(y), word, M, C, int(relu), _stream())
-            pl_tag(y, word)
-        elif pool:
-            h2_mark_next(y)
-            call("tris_bn_apply_pool_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(y), x.shape[0], x.shape[1], x.shape[2], C,
-                 _stream())
-        elif not lazy:
-            h2_mark_next(y)
-            call("tris_bn_apply_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(resid), P(y), M, C, int(relu),
-                 _stream())
-        if lazy:   # the hand-off to ops.conv3x3 rides on the (unwritten) output tensor itself
-            # h2: the consuming convolution needs an operand scale for a tensor that never exists -- an upper bound of |y| from the
-            # affine parameters alone (Samuelson: |xhat| <= sqrt(n - 1)), as an amax word that travels with the hand-off
-            y._bn_lazy = (x, mean, invstd, gamma, beta, h2_bound_word(gamma, beta, C, math.sqrt(max(count - 1, 1))))
-        ctx.cfg = (M, C, bool(relu), resid is not None, count, group)
-        ctx.grad_box = grad_box
-        ctx.params = (gamma, beta)
-        ctx.training = bool(training)
-        ctx.link = None
-        ctx.pair = pr
-        if not pair_out:
-            ctx.pair_state = None
-        ctx.pool = pool
+            ctx.pair_state = _BnPairState(plan.dx_pl, tuple(ctx.needs_input_grad[:3]))
+            y._bn_pair = _BnPair(*bn, word, ctx.pair_state)
+        else:
+            y_mask = _bn_apply(o, plan, bn, resid, y, word, rw)
+        if plan.lazy:   # the hand-off to ops.conv3x3 rides on the (unwritten) output tensor itself
+            # h2: the consuming convolution needs an operand scale for a tensor that never exists -- an upper bound of |relu(bn(x))|
+            # from the affine parameters alone, as an amax word that travels with the hand-off (None: not h2)
+            bound = _h2_slot() if h2_on() else None
+            if bound is not None:
+                call("tris_bn_out_bound_f32", P(gamma), P(beta), C, xmax, bound, _stream())
+            y._bn_lazy = _BnLazy(*bn, bound)
+        ctx.cfg = (M, C, bool(o.relu), resid is not None, count, o.group)
+        ctx.grad_box, ctx.params, ctx.training = o.grad_box, (gamma, beta), bool(o.training)
+        ctx.dx_pl, ctx.pool, ctx.pair, ctx.link = plan.dx_pl, bool(o.pool), pr, None
         ctx.y_pl = getattr(y, "_pl", None)
-        if training:
-            keep_y = relu and not pool and resid is not None
-            ctx.save_for_backward(x, gamma, beta, mean, invstd, y if keep_y else None)
-            if bwd_link and relu and not pool:
+        if o.training:
+            keep_y = o.relu and not o.pool and resid is not None
+            ctx.save_for_backward(x, gamma, beta, bn.mean, bn.invstd, y if keep_y else None)
+            if o.bwd_link and o.relu and not o.pool:
                 # the consumer (ops.linear) may reduce this BatchNorm's backward sums in its data-gradient epilogue: _BnBwdLink
-                ctx.link = y._bn_link = _BnBwdLink(x, mean, invstd, gamma, beta, keep_y)
+                ctx.link = y._bn_link = _BnBwdLink(*bn, keep_y)
                 ctx.link.mask = y_mask if keep_y else None
                 ctx.link.pair = pr if keep_y else None
         return y
 
     @staticmethod
     def backward(ctx, dy):
+        """The steps: take the link; the two sums (finalized from the product's partial rows, or _bn_bwd_reduce); the SyncBN exchange or
+        the parameter gradients; apply (_bn_bwd_apply, or the pair pass)"""
         if not ctx.training:
             raise NotImplementedError("BatchNorm in eval mode is forward-only on this path")
         x, gamma, beta, mean, invstd, y = ctx.saved_tensors
         M, C, relu, has_res, count, group = ctx.cfg
-        done = ctx.pair_state.pop("done", None) if ctx.pair_state is not None else None
-        if done is not None:
+        st = ctx.pair_state
+        if st is not None and st.done is not None:
             # the shortcut BatchNorm of a pair whose bn3 backward has done this one's as well (below): dx is written, the sums formed
-            dxs, in_arena_s, sums_s = done
-            dg = db = None
-            if not in_arena_s:
-                dg = _emit(ctx.params[0], lambda o: o.copy_(sums_s[C:]), ctx.needs_input_grad[1])
-                db = _emit(ctx.params[1], lambda o: o.copy_(sums_s[:C]), ctx.needs_input_grad[2])
-            return (dxs, dg, db) + (None,) * 16
+            (dxs, in_arena_s, sums_s), st.done = st.done, None
+            dg, db = (None, None) if in_arena_s else _bn_param_grads(ctx, sums_s, C)
+            return dxs, dg, db, None, None, None, None
         dy = unplanes(pl_grad_in(dy.contiguous()))   # (the gradient of a BatchNorm OUTPUT is fp32 on every path of the trunk)
         _retag(y, ctx.y_pl)
-        y_is_pl = pl_word(y) is not None
+        b = _BnBwd(x, mean, invstd, gamma, beta, M, C, ctx.pool, 1.0 / float(count), math.sqrt(max(count - 1, 1)))
+        need_dx = ctx.needs_input_grad[0]
         dx_pl = ctx.dx_pl and planes_on()
         dzw = _h2_slot() if dx_pl else None    # amax word of the masked gradient dz: left by whichever pass reduces it
-        d_res = None
+        dx = dg = db = d_res = None
         want_dz = has_res and ctx.needs_input_grad[5]
         if has_res and not relu:
             d_res, want_dz = (dy if want_dz else None), False
         # out = relu(bn(x) + resid): both branches see dz = dy * (out > 0); the mask is applied inside the reduce / apply
         # kernels and the apply kernel emits dz for the residual branch in the same pass
-        ws = workspace(query("tris_col_workspace_bytes", M, C))
         sg, sb = _sink(ctx.params[0]), _sink(ctx.params[1])
         in_arena = (sg is not None and sb is not None and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]
                     and sg.is_contiguous() and sb.is_contiguous())
@@ -1923,161 +2015,102 @@ class BatchNormFn(torch.autograd.Function):
             from . import comm
             mb = comm.syncbn_mailbox(group, 2 * C)
         direct = in_arena and (group is None or mb is not None)
-        if direct:   # the two LOCAL reductions ARE dbeta / dgamma: write them straight into the gradient arena
-            p_dz, p_dzx = P(sb), P(sg)
-            dg = db = None
-        else:
-            sums = torch.empty(2 * C, device=x.device, dtype=torch.float32)
-            p_dz, p_dzx = P(sums), P(sums, C)
+        # direct: the two LOCAL reductions ARE dbeta / dgamma, written straight into the gradient arena (mb: the sums over all ranks)
+        sums = torch.empty(2 * C, device=x.device, dtype=torch.float32) if (mb is not None or not direct) else None
+        p_dz, p_dzx = (P(sb), P(sg)) if direct else (P(sums), P(sums, C))
         # BatchNorm + ReLU without a residual: the mask is recomputed from x inside the kernels, y is not read
         mask_x = relu and not has_res and y is None
         # residual blocks (out = relu(bn(x) + identity)): the reduce pass writes the masked gradient dz -- which IS the identity
         # branch's gradient -- and the apply pass reads it back instead of masking dy from y a second time
         got = ctx.link.take(dy) if ctx.link is not None else None
         if got is not None and dx_pl:
-            dzw = got[2] if got[2] is not None else _h2_amax(dy)
-        if ctx.pool:   # dy is the POOLED gradient: both passes read it in place of a full-size tensor (mask from x)
-            Bn, H, W = x.shape[0], x.shape[1], x.shape[2]
-            if dzw is not None:
-                call("tris_amax_next", dzw)
-            call("tris_bn_bwd_reduce_pool_f32", P(dy), P(x), P(mean), P(invstd), Bn, H, W, C, p_dz, p_dzx, P(ws), P(gamma), P(beta),
-                 _stream())
+            dzw = got.dzw if got.dzw is not None else _h2_amax(dy)
         dz_first = got is None and not ctx.pool and want_dz and relu and y is not None
         if dz_first:
             d_res = torch.empty_like(x)
         bound_word = None     # (operand planes: dx's bound word when the finalizer below formed it)
-        if got is not None and dx_pl and mb is None and (direct or group is None) and ctx.needs_input_grad[0]:
+        if got is not None and dx_pl and mb is None and (direct or group is None) and need_dx:
             bound_word = _h2_slot()
         # cfg.bn_pair: the product that left bn3's sums also left sum(dz * xhat_s) of the shortcut BatchNorm, which receives the same
         # masked gradient: one finalizer launch for both, one apply pass that reads dz once and writes both input gradients
         pair, pair_word = ctx.pair, None
-        if (pair is not None and got is not None and got[3] is not None and bound_word is not None and group is None and want_dz
-                and pair[6].get("dx_pl") and all(pair[6].get("needs", ()))):
+        if (pair is not None and got is not None and got.part2 is not None and bound_word is not None and group is None and want_dz
+                and pair.state.dx_pl and all(pair.state.needs)):
             pair_word = _h2_slot()
         if pair_word is not None:
-            gs, bs = pair[3], pair[4]
-            sgs, sbs = _sink(gs), _sink(bs)
+            sgs, sbs = _sink(pair.gamma), _sink(pair.beta)
             in_arena_s = sgs is not None and sbs is not None and sgs.is_contiguous() and sbs.is_contiguous()
             sums_s = None if in_arena_s else torch.empty(2 * C, device=x.device, dtype=torch.float32)
-            call("tris_part_finalize_pair_f32", got[0].data_ptr(), got[3].data_ptr(), got[1], C, p_dz, p_dzx,
-                 P(sbs) if in_arena_s else P(sums_s), P(sgs) if in_arena_s else P(sums_s, C), P(gamma), P(invstd), P(gs), P(pair[2]),
-                 1.0 / float(count), math.sqrt(max(count - 1, 1)), dzw, bound_word, pair_word, _stream())
+            ps_dz, ps_dzx = (P(sbs), P(sgs)) if in_arena_s else (P(sums_s), P(sums_s, C))
+            call("tris_part_finalize_pair_f32", got.part.data_ptr(), got.part2.data_ptr(), got.rows, C, p_dz, p_dzx, ps_dz, ps_dzx, P(gamma),
+                 P(invstd), P(pair.gamma), P(pair.invstd), b.inv_cnt, b.xmax, dzw, bound_word, pair_word, _stream())
         elif got is not None and bound_word is not None:
-            call("tris_part_finalize_bound_f32", got[0].data_ptr(), got[1], C, p_dz, p_dzx, P(gamma), P(invstd), 1.0 / float(count),
-                 math.sqrt(max(count - 1, 1)), dzw, bound_word, _stream())
+            call("tris_part_finalize_bound_f32", got.part.data_ptr(), got.rows, C, p_dz, p_dzx, P(gamma), P(invstd), b.inv_cnt, b.xmax, dzw,
+                 bound_word, _stream())
         elif got is not None:
             # dy came out of the consuming 1x1 convolution's data gradient already MASKED, with the two sums as partial rows
-            call("tris_part_finalize_f32", got[0].data_ptr(), got[1], C, p_dz, p_dzx, _stream())
-        elif not ctx.pool:
-            if dzw is not None:
-                call("tris_amax_next", dzw)
-            if y_is_pl and not mask_x:
-                call("tris_bn_bwd_reduce_pl_f32", P(dy), P(y), P(x), P(mean), P(invstd), M, C, p_dz, p_dzx, P(ws),
-                     P(d_res) if dz_first else None, _stream())
-            else:
-                call("tris_bn_bwd_reduce_f32", P(dy), None if mask_x else P(y), P(x), P(mean), P(invstd), M, C, p_dz, p_dzx, P(ws),
-                     P(gamma) if mask_x else None, P(beta) if mask_x else None, P(d_res) if dz_first else None, _stream())
+            call("tris_part_finalize_f32", got.part.data_ptr(), got.rows, C, p_dz, p_dzx, _stream())
+        else:
+            _bn_bwd_reduce(b, dy, y, mask_x, p_dz, p_dzx, dzw, d_res if dz_first else None)
         if mb is not None:
             # SyncBatchNorm: the arena keeps this rank's dbeta / dgamma (the data-parallel reducer averages them like every
             # other gradient); the sums over ALL ranks that dX needs come from one peer-mailbox launch reading the arena
-            sums = torch.empty(2 * C, device=x.device, dtype=torch.float32)
-            if dx_pl and dzw is not None and ctx.needs_input_grad[0] and bound_word is None and cfg.syncbn_bound:
+            if dx_pl and dzw is not None and need_dx and bound_word is None and cfg.syncbn_bound:
                 bound_word = _h2_slot()
             if bound_word is not None and dx_pl and dzw is not None:   # the same launch leaves the bound word of dx
-                mb.bn_bwd_exchange(sb, sg, sums, gamma, invstd, 1.0 / float(count), math.sqrt(max(count - 1, 1)), dzw, bound_word)
+                mb.bn_bwd_exchange(sb, sg, sums, gamma, invstd, b.inv_cnt, b.xmax, dzw, bound_word)
             else:
                 mb.exchange(sb, sums, 1, src1=sg)
             p_dz, p_dzx = P(sums), P(sums, C)
         elif not direct:
-            dg = _emit(ctx.params[0], lambda o: o.copy_(sums[C:]), ctx.needs_input_grad[1])
-            db = _emit(ctx.params[1], lambda o: o.copy_(sums[:C]), ctx.needs_input_grad[2])
+            dg, db = _bn_param_grads(ctx, sums, C)
             if group is not None:
                 from . import comm
                 comm.syncbn_all_reduce_sum(sums, group=group)
-        dx = None
-        inv_cnt = 1.0 / float(count)
-
-        def apply(g, ymask, dz_out, beta_m):
-            """dx from the (masked or to-be-masked) gradient g; as operand planes where the convolution before takes them"""
-            if dx_pl:
-                word = bound_word
-                if word is None:
-                    word = _h2_slot()
-                    call("tris_bn_bwd_bound_f32", P(gamma), P(invstd), p_dz, p_dzx, C, inv_cnt, math.sqrt(max(count - 1, 1)), dzw, word,
-                         _stream())
-                if ctx.pool:
-                    call("tris_bn_bwd_apply_pool_pl_f32", P(g), P(x), P(mean), P(invstd), P(gamma), P(beta), p_dz, p_dzx, inv_cnt, P(dx),
-                         word, x.shape[0], x.shape[1], x.shape[2], C, _stream())
-                else:
-                    if ymask is not None and not y_is_pl:
-                        raise RuntimeError("operand planes: the ReLU mask of a plane-output BatchNorm must come from plane y")
-                    call("tris_bn_bwd_apply_pl_f32", P(g), P(ymask), P(x), P(mean), P(invstd), P(gamma), p_dz, p_dzx, inv_cnt, P(dx),
-                         word, P(dz_out), M, C, P(beta_m), _stream())
-                pl_grad_out(dx, word)
-                return
-            h2_mark_next(dx)
-            if ctx.pool:
-                call("tris_bn_bwd_apply_pool_f32", P(g), P(x), P(mean), P(invstd), P(gamma), P(beta), p_dz, p_dzx, inv_cnt, P(dx),
-                     x.shape[0], x.shape[1], x.shape[2], C, _stream())
-            else:
-                call("tris_bn_bwd_apply_f32", P(g), P(unplanes(ymask)) if ymask is not None else None, P(x), P(mean), P(invstd),
-                     P(gamma), p_dz, p_dzx, inv_cnt, P(dx), P(dz_out), M, C, P(beta_m), _stream())
-        if ctx.pool:
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                apply(dy, None, None, None)
-        elif got is not None and pair_word is not None:
+        if pair_word is not None:
             d_res = dy              # (what autograd routes to the shortcut BatchNorm's node; that node finds its work done)
             dx, dxs = torch.empty_like(x), torch.empty_like(x)
-            call("tris_bn_bwd_apply_pair_pl_f32", P(dy), P(x), P(mean), P(invstd), P(gamma), p_dzx, P(pair[0]), P(pair[1]), P(pair[2]),
-                 P(gs), P(sgs) if in_arena_s else P(sums_s, C), p_dz, inv_cnt, P(dx), bound_word, P(dxs), pair_word, M, C, _stream())
+            call("tris_bn_bwd_apply_pair_pl_f32", P(dy), P(x), P(mean), P(invstd), P(gamma), p_dzx, P(pair.x), P(pair.mean), P(pair.invstd),
+                 P(pair.gamma), ps_dzx, p_dz, b.inv_cnt, P(dx), bound_word, P(dxs), pair_word, M, C, _stream())
             pl_grad_out(dx, bound_word)
             pl_grad_out(dxs, pair_word)
-            pair[6]["done"] = (dxs, in_arena_s, sums_s)
-        elif got is not None:
-            if want_dz:
+            pair.state.done = (dxs, in_arena_s, sums_s)
+        elif ctx.pool or got is not None or dz_first:
+            if got is not None and want_dz:
                 d_res = dy          # the masked gradient IS the identity branch's gradient
-            if ctx.needs_input_grad[0]:
+            if need_dx:
                 dx = torch.empty_like(x)
-                apply(dy, None, None, None)
-        elif dz_first:
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-                apply(d_res, None, None, None)
-        elif ctx.needs_input_grad[0] or want_dz:
+                _bn_bwd_apply(b, d_res if dz_first else dy, None, None, None, dx, p_dz, p_dzx, dzw, bound_word, dx_pl)
+        elif need_dx or want_dz:
             dx = torch.empty_like(x)
             if want_dz:
                 d_res = torch.empty_like(x)
-            apply(dy, None if mask_x else y, d_res if want_dz else None, beta if mask_x else None)
+            _bn_bwd_apply(b, dy, None if mask_x else y, d_res if want_dz else None, beta if mask_x else None, dx, p_dz, p_dzx, dzw,
+                          bound_word, dx_pl)
         if ctx.grad_box is not None and d_res is not None and ctx.grad_box.deposit(d_res):
             d_res = None   # handed to the block's first conv
-        return dx, dg, db, None, None, d_res, None, None, None, None, None, None, None, None, None, None, None, None, None
-
-
-def _bn_pair_write(pr):
-    """the fp32 output of a shortcut BatchNorm that was handed over as `_bn_pair`, for a bn3 that cannot take the pair after all"""
-    x, mean, invstd, gamma, beta = pr[:5]
-    y = torch.empty_like(x)
-    h2_mark_next(y)
-    call("tris_bn_apply_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), None, P(y), x.numel() // x.shape[-1], x.shape[-1], 0, _stream())
-    return y
+        return dx, dg, db, None, None, d_res, None
 
 
 def batch_norm(x, gamma, beta, rmean, rvar, resid=None, relu=False, training=True, momentum=0.1, eps=1e-5, group=None,
                grad_box=None, lazy=False, bwd_link=False, pool=False, planes=False, dx_planes=False, pair=False):
     """lazy=True (train-mode BatchNorm + ReLU whose ONLY consumer is ops.conv3x3, and conv3x3_bnin_ok said yes): the returned
     tensor is an unwritten buffer carrying `_bn_lazy`; pass it to ops.conv3x3 and nowhere else.
-    planes / dx_planes (h2 with operand planes, train mode): the output / the input gradient is written as fp16 operand planes --
-    the caller vouches that every consumer takes them (BatchNormFn.forward)."""
+    planes / dx_planes (h2 with operand planes, train mode): the output is WRITTEN as fp16 operand planes -- the caller vouches that
+    every consumer is a product, a plane-aware BatchNorm / pool, or goes through ops.unplanes -- and so is the input gradient (its one
+    consumer is the backward of the convolution before).
+    pair (the shortcut BatchNorm of a down-sampling Bottleneck; cfg.bn_pair): the output's ONLY reader is the block's bn3, as its
+    residual -- where the plane path applies the statistics are formed here, the output is NOT written, and what comes back is an
+    unallocated stand-in carrying `_bn_pair`; bn3's pass normalises the shortcut's raw input itself (tris_bn_apply_pair_pl_f32).
+    pool: the output is avgpool2(relu(bn(x))) -- BatchNorm + ReLU + AvgPool2d(2) as one op, the full-size tensor never written (needs
+    train mode, ReLU, no residual, an even map: otherwise the two ops one after the other)."""
     part = getattr(x, "_bn_part", None) if training else None
-    bwd_link = bool(bwd_link and training and torch.is_grad_enabled() and x.requires_grad and _bn_bwd_fuse_enabled())
+    bwd_link = bool(bwd_link and training and torch.is_grad_enabled() and x.requires_grad and cfg.bn_bwd_fuse)
+    o = _BnOpts(relu, training, momentum, eps, group, part, grad_box, lazy, bwd_link, bool(pool), planes, dx_planes, pair)
     if pool and not (training and relu and resid is None and not lazy and x.dim() == 4 and x.shape[1] % 2 == 0
                      and x.shape[2] % 2 == 0 and cfg.bn_pool):
-        # eval mode / shapes the fused op does not take: the two ops one after the other
-        return avgpool2(BatchNormFn.apply(x, gamma, beta, rmean, rvar, resid, relu, training, momentum, eps, group, part, grad_box,
-                                          lazy, bwd_link, False, planes, dx_planes, pair))
-    return BatchNormFn.apply(x, gamma, beta, rmean, rvar, resid, relu, training, momentum, eps, group, part, grad_box, lazy,
-                             bwd_link, pool, planes, dx_planes, pair)
+        return avgpool2(BatchNormFn.apply(x, gamma, beta, rmean, rvar, resid, o._replace(pool=False)))
+    return BatchNormFn.apply(x, gamma, beta, rmean, rvar, resid, o)
 
 
 class AvgPool2Fn(torch.autograd.Function):
@@ -3139,11 +3172,7 @@ class BnPreluFn(torch.autograd.Function):
         M = x.numel() // C
         if training:
             stats = torch.empty(3 * C, device=x.device, dtype=torch.float32)
-            if part is not None:
-                call("tris_bn_finalize_f32", part[0].data_ptr(), part[1], M, C, eps, momentum, P(stats), P(rmean), P(rvar), _stream())
-            else:
-                ws = workspace(query("tris_col_workspace_bytes", M, C))
-                call("tris_bn_stats_f32", P(x), M, C, eps, momentum, P(stats), P(rmean), P(rvar), P(ws), _stream())
+            _bn_local_stats(x, part, eps, momentum, stats, rmean, rvar)
             mean, invstd = stats[:C], stats[C:2 * C]
         else:
             mean, invstd = rmean, torch.rsqrt(rvar + eps)

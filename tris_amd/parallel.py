@@ -234,12 +234,8 @@ class GradReducer:
     def boundary(self, x, key):
         if not self.active or not torch.is_grad_enabled() or not x.requires_grad:
             return x
-        y = _Boundary.apply(x, self, key)
-        for attr in ("_bn_link", "_pl", "_h2"):   # (ops._BnBwdLink / the plane tag ride on the tensor: the boundary is an identity)
-            v = getattr(x, attr, None)
-            if v is not None:
-                setattr(y, attr, v)
-        return y
+        from . import ops
+        return ops.carry(x, _Boundary.apply(x, self, key))   # (ops._BnBwdLink / the plane tag ride on the tensor: the boundary is an identity)
 
     def finish(self):
         """Launch every segment not yet launched, wait for all, reset for the next step."""
