@@ -307,14 +307,24 @@ int tris_bn_bwd_apply_f32(const float* dY, const float* Y, const float* X, const
 int tris_colsum_f32(const float* X, long M, int N, long ld, float* out, float* workspace, void* stream);
 
 /* ---- InstanceNorm2d(affine) [+ReLU] on [B, P, C]  (model/attn.py:75,80,85,106) ----------------------------------------
- * (both honour tris_amax_next: the amax word of Y / dX as a by-product) */
+ * (both honour tris_amax_next: the amax word of Y / dX as a by-product)
+ * Biased two-pass variance over the P pixels of a (b, c); the forward stores the mean and invstd = rsqrt(var + eps) it used.  The
+ * backward's ReLU mask is Y > 0 of the saved output; dgamma_part / dbeta_part are the sums of one image, summed over b by the caller.
+ * Contract (hipErrorInvalidValue before any launch otherwise): B, P, C >= 1 (any C, any P); forward: X, gamma, beta, Y, mean, invstd
+ * non-NULL; backward: dY, X, gamma, mean, invstd, dX, dgamma_part, dbeta_part non-NULL, and Y non-NULL when relu != 0. */
 int tris_instnorm_fwd_f32(const float* X, const float* gamma, const float* beta, float* Y, float* mean, float* invstd,
                           int B, int P, int C, float eps, int relu, void* stream);
 int tris_instnorm_bwd_f32(const float* dY, const float* Y, const float* X, const float* gamma, const float* mean,
                           const float* invstd, float* dX, float* dgamma_part /*[B,C]*/, float* dbeta_part /*[B,C]*/,
                           int B, int P, int C, int relu, void* stream);
 
-/* ---- LayerNorm over the last dim W <= 1024  (CLIP/clip/model.py:352-358) ------------------------------------------------ */
+/* ---- LayerNorm over the last dim W <= 1024  (CLIP/clip/model.py:352-358) ------------------------------------------------
+ * Biased two-pass variance; the forward stores the mean and rstd = rsqrt(var + eps) it used (both, or neither: mean = rstd = NULL).
+ * The backward writes dX = rstd (dy g - c1 - xhat c2) [+ extra], dgamma = sum_rows dy xhat, dbeta = sum_rows dy; dX == NULL or
+ * dgamma == dbeta == NULL leaves that part out.  Both honour tris_amax_next (Y / dX), the forward tris_rows_limit_thread.
+ * Contract (hipErrorInvalidValue before any launch otherwise): rows >= 1, 4 <= W <= 1024, W % 4 == 0; forward: X, gamma, beta, Y
+ * non-NULL, mean and rstd both NULL or both non-NULL; backward: dY, X, gamma, mean, rstd non-NULL, dgamma and dbeta both NULL or
+ * both non-NULL, workspace (tris_layernorm_bwd_workspace_bytes) non-NULL when dgamma is, and not dX == NULL with dgamma == NULL. */
 int tris_layernorm_fwd_f32(const float* X, const float* gamma, const float* beta, float* Y, float* mean, float* rstd,
                            long rows, int W, float eps, void* stream);
 long tris_layernorm_bwd_workspace_bytes(long rows, int W);
@@ -414,11 +424,16 @@ int tris_eot_gather_fwd_f32(const long* ids, const float* x, float* out, int N, 
 int tris_eot_gather_bwd_f32(const long* ids, const float* dout, float* dx, int N, int L, int W, void* stream);
 
 /* ---- Stage-1 heads ------------------------------------------------------------------------------------------------- */
-/* x / x.norm(dim=-1)  (model_stage1.py:68-69; train_stage1.py:268-269) */
+/* x / x.norm(dim=-1)  (model_stage1.py:68-69; train_stage1.py:268-269).  No eps, as the reference has none: the domain is rows
+ * whose sum of squares neither underflows nor overflows float32 (row norms between 2^-40 and 2^40 are inside it; a zero row gives
+ * inv_norm = inf and NaNs).  Backward from the saved Y and inv_norm: dX = (dY - Y sum(Y dY)) inv_norm.
+ * Contract (hipErrorInvalidValue before any launch otherwise): rows >= 1, C >= 1, every pointer non-NULL. */
 int tris_l2norm_fwd_f32(const float* X, float* Y, float* inv_norm, long rows, int C, void* stream);
 int tris_l2norm_bwd_f32(const float* dY, const float* Y, const float* inv_norm, float* dX, long rows, int C,
                         void* stream);
-/* softmax(scale * x) over rows of length n  (model/attn.py:119,122) */
+/* softmax(scale * x) over rows of length n  (model/attn.py:119,122); the maximum is taken of the SCALED logits (any sign of scale).
+ * Backward from the saved Y: dX = scale Y (dY - sum(Y dY)).
+ * Contract (hipErrorInvalidValue before any launch otherwise): rows >= 1, n >= 1, every pointer non-NULL, scale finite. */
 int tris_softmax_fwd_f32(const float* X, float* Y, long rows, int n, float scale, void* stream);
 int tris_softmax_bwd_f32(const float* dY, const float* Y, float* dX, long rows, int n, float scale, void* stream);
 /* Fused image<->text cross attention of bilateral_prompt (model/attn.py:117-128), all images in two (x3 arithmetic) or

@@ -452,24 +452,28 @@ inline int grid_for(long n, int block = 256) {
 }  // namespace
 
 extern "C" int tris_l2norm_fwd_f32(const float* X, float* Y, float* inv_norm, long rows, int C, void* stream) {
+  if (rows < 1 || C < 1 || !X || !Y || !inv_norm) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(l2norm_fwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, X, Y, inv_norm, rows, C);
   TRIS_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int tris_l2norm_bwd_f32(const float* dY, const float* Y, const float* inv_norm, float* dX, long rows, int C,
                                    void* stream) {
+  if (rows < 1 || C < 1 || !dY || !Y || !inv_norm || !dX) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, dY, Y, inv_norm, dX,
                      rows, C);
   TRIS_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int tris_softmax_fwd_f32(const float* X, float* Y, long rows, int n, float scale, void* stream) {
+  if (rows < 1 || n < 1 || !X || !Y || !__builtin_isfinite(scale)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(softmax_fwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, X, Y, rows, n, scale);
   TRIS_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int tris_softmax_bwd_f32(const float* dY, const float* Y, float* dX, long rows, int n, float scale,
                                     void* stream) {
+  if (rows < 1 || n < 1 || !dY || !Y || !dX || !__builtin_isfinite(scale)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(softmax_bwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, dY, Y, dX, rows, n,
                      scale);
   TRIS_LAUNCH_CHECK();

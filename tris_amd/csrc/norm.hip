@@ -1166,6 +1166,7 @@ extern "C" int tris_colsum_f32(const float* X, long M, int N, long ld, float* ou
 
 extern "C" int tris_instnorm_fwd_f32(const float* X, const float* gamma, const float* beta, float* Y, float* mean,
                                      float* invstd, int B, int P, int C, float eps, int relu, void* stream) {
+  if (B < 1 || P < 1 || C < 1 || !X || !gamma || !beta || !Y || !mean || !invstd) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(instnorm_fwd_kernel, dim3(cdiv(C, 64), B), dim3(256), 0, (hipStream_t)stream, X, gamma, beta, Y,
                      mean, invstd, P, C, eps, relu, take_amax_next());
   TRIS_LAUNCH_CHECK();
@@ -1175,6 +1176,8 @@ extern "C" int tris_instnorm_fwd_f32(const float* X, const float* gamma, const f
 extern "C" int tris_instnorm_bwd_f32(const float* dY, const float* Y, const float* X, const float* gamma,
                                      const float* mean, const float* invstd, float* dX, float* dgamma_part,
                                      float* dbeta_part, int B, int P, int C, int relu, void* stream) {
+  if (B < 1 || P < 1 || C < 1 || !dY || !X || !gamma || !mean || !invstd || !dX || !dgamma_part || !dbeta_part || (relu && !Y))
+    return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(instnorm_bwd_kernel, dim3(cdiv(C, 64), B), dim3(256), 0, (hipStream_t)stream, dY, Y, X, gamma,
                      mean, invstd, dX, dgamma_part, dbeta_part, P, C, relu, take_amax_next());
   TRIS_LAUNCH_CHECK();
@@ -1183,7 +1186,8 @@ extern "C" int tris_instnorm_bwd_f32(const float* dY, const float* Y, const floa
 
 extern "C" int tris_layernorm_fwd_f32(const float* X, const float* gamma, const float* beta, float* Y, float* mean,
                                       float* rstd, long rows, int W, float eps, void* stream) {
-  if (W % 4 || W > 1024) return (int)hipErrorInvalidValue;
+  if (W % 4 || W > 1024 || W < 4 || rows < 1 || !X || !gamma || !beta || !Y || (mean == nullptr) != (rstd == nullptr))
+    return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, X, gamma, beta, Y,
                      mean, rstd, rows, W, eps, take_amax_next(), g_rows_limit);
   TRIS_LAUNCH_CHECK();
@@ -1210,7 +1214,9 @@ extern "C" long tris_layernorm_bwd_workspace_bytes(long rows, int W) {
 extern "C" int tris_layernorm_bwd_f32(const float* dY, const float* X, const float* gamma, const float* mean,
                                       const float* rstd, float* dX, float* dgamma, float* dbeta, long rows, int W,
                                       float* workspace, const float* extra, void* stream) {
-  if (W % 4 || W > 1024) return (int)hipErrorInvalidValue;
+  if (W % 4 || W > 1024 || W < 4 || rows < 1 || !dY || !X || !gamma || !mean || !rstd || (dgamma == nullptr) != (dbeta == nullptr) ||
+      (dgamma && !workspace) || (!dX && !dgamma))
+    return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   const long rpb = ln_bwd_rpb(rows);
   int nb = (int)((rows + rpb - 1) / rpb);
