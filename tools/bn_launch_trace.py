@@ -45,12 +45,12 @@ def _classify(name, args):
 
 
 @contextlib.contextmanager
-def recording(calls):
+def recording(calls, classify=_classify):
     """every ops.call / ops._declinable of the scope, classified, appended to `calls`"""
     from tris_amd import ops
     call, declinable = ops.call, ops._declinable
-    ops.call = lambda name, *a: (calls.append(_classify(name, a)), call(name, *a))[1]
-    ops._declinable = lambda name, *a: (calls.append(_classify(name, a)), declinable(name, *a))[1]
+    ops.call = lambda name, *a: (calls.append(classify(name, a)), call(name, *a))[1]
+    ops._declinable = lambda name, *a: (calls.append(classify(name, a)), declinable(name, *a))[1]
     try:
         yield calls
     finally:

@@ -12,6 +12,7 @@ Weight gradients: a parameter may carry a "gradient sink" (`p.grad` is a view in
 see tris_amd.optim).  Backward kernels then write the weight gradient straight into that arena
 (each parameter is used once per step) and return None to autograd.
 """
+import ctypes
 import math
 import os
 from typing import NamedTuple, Optional
@@ -512,40 +513,19 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, tA, tB, batch=1, sA=0, sB=0, sC=0, bia
     if pre_out is not None or dact is not None or batch != 1 or _BATCH_INVARIANT:
         A, B = unplanes(A), unplanes(B)
     if pre_out is not None or dact is not None:
-        if _BATCH_INVARIANT or batch != 1:
-            return False
-        h2_arm(A, B)
-        h2_mark_next(C)
-        call("tris_gemm_epilogue_next", P(pre_out), P(dact))
-        return _timed("gemm", 2.0 * M * N * K, lambda: _declinable(
-            "tris_gemm_f32", P(A), P(B), P(C), M, N, K, lda, ldb, ldc, int(tA), int(tB), 1, 0, 0, 0, P(bias), bias_mode, P(resid),
-            ldr, sR, act, float(alpha), None, 0, _stream()),
-            nbytes=4.0 * (M * K + K * N + M * N * (2 + int(resid is not None))))
+        return _gemm_epilogue(A, B, C, M, N, K, lda, ldb, ldc, tA, tB, batch, bias, bias_mode, resid, ldr, sR, act, alpha, pre_out, dact)
     if _BATCH_INVARIANT and batch == 1 and not tA and M < 4 and lda == K and ldc == N and (resid is None or ldr == N) and bias_mode != 2:
-        # products of fewer than four rows run a different (generic) kernel than larger ones: in batch-invariant mode they are
-        # padded to four rows so that a sentence evaluated alone goes through the same arithmetic as one evaluated in a batch
-        A4 = A.new_zeros(4, K)
-        A4[:M].copy_(A.reshape(M, K))
-        R4 = None
-        if resid is not None:
-            R4 = resid.new_zeros(4, N)
-            R4[:M].copy_(resid.reshape(M, N))
-        C4 = C.new_empty(4, N)
-        gemm(A4, B, C4, 4, N, K, K, ldb, N, False, tB, bias=bias, bias_mode=bias_mode, resid=R4, ldr=N, act=act, alpha=alpha,
-             use_ws=use_ws)
-        C.reshape(M, N).copy_(C4[:M])
-        return C
+        return _gemm_padded(A, B, C, M, N, K, ldb, tB, bias, bias_mode, resid, act, alpha, use_ws)
     ws = workspace(0) if (use_ws and batch == 1 and not _BATCH_INVARIANT) else None   # (no workspace = no split-K)
     blind = _rows_limit_blind(A, tA, batch)
     if (w_b and batch == 1 and not tA and M >= cfg.gemm_convert and cfg.gemm_convert > 0 and K % 32 == 0 and lda == K and getattr(B, "_tris_linear_w", False)
             and planes_on() and pl_word(A) is None and A.is_contiguous() and A.data_ptr() % 16 == 0 and _pl_weight_ok(B) and not blind):
         A = _a_planes(A, M, K)
-    if blind:
-        PL_STATS["last"] = PL_STATS["last_t"] = False
-        pA, pB = P(A), P(unplanes(B))
+    if blind or batch != 1:     # (a batched product's operands were rebuilt above)
+        pp = _Operands(P(A), P(unplanes(B)), False, False)
     else:
-        pA, pB = h2_pp(A, B, w_a=w_a, w_b=w_b, k_red=K, w_bt=w_bt and not tB) if batch == 1 else (P(A), P(B))
-    if batch == 1 and PL_STATS["last_t"]:    # B = W [K][N] arrived as the planes of its transpose [N][K]
+        pp = h2_pp(A, B, w_a=w_a, w_b=w_b, k_red=K, w_bt=w_bt and not tB)
+    if pp.b_t:    # B = W [K][N] arrived as the planes of its transpose [N][K]
         tB, ldb = True, K
     if mark:
         h2_mark_next(C)  # (h2: the product also leaves the amax of what it writes -- another product may consume C directly)
@@ -555,13 +535,45 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, tA, tB, batch=1, sA=0, sB=0, sC=0, bia
             call("tris_splitk_tickets_next", tk.data_ptr(), tk.numel())
     if resid_pool is not None:
         call("tris_gemm_resid_pool_next", resid_pool[0], resid_pool[1])
-    ran = _timed("gemm", 2.0 * M * N * K * batch, lambda: (_declinable if resid_pool is not None else call)(
-        "tris_gemm_f32", pA, pB, P(C), M, N, K, lda, ldb, ldc, int(tA), int(tB), batch, sA, sB, sC, P(bias),
-        bias_mode, P(resid), ldr, sR, act, float(alpha), P(ws), 0 if ws is None else ws.numel() * 4, _stream()),
-        tag=(f"{'T' if tA else 'N'}{'T' if tB else 'N'} M{M} N{N} K{K} b{batch}" if _PROF_SHAPES else None),
-        nbytes=4.0 * ((M * K if (sA == 0 and batch > 1) else batch * M * K) + batch * K * N
-                      + batch * M * N * (2 if resid is not None else 1)))
+
+    def launch():
+        return (_declinable if resid_pool is not None else call)(
+            "tris_gemm_f32", pp.a, pp.b, P(C), M, N, K, lda, ldb, ldc, int(tA), int(tB), batch, sA, sB, sC, P(bias), bias_mode, P(resid),
+            ldr, sR, act, float(alpha), P(ws), 0 if ws is None else ws.numel() * 4, _stream())
+    ran = _timed("gemm", 2.0 * M * N * K * batch, launch,
+                 tag=(f"{'T' if tA else 'N'}{'T' if tB else 'N'} M{M} N{N} K{K} b{batch}" if _PROF_SHAPES else None),
+                 nbytes=4.0 * ((M * K if (sA == 0 and batch > 1) else batch * M * K) + batch * K * N
+                               + batch * M * N * (2 if resid is not None else 1)))
     return False if ran is False else C
+
+
+def _gemm_epilogue(A, B, C, M, N, K, lda, ldb, ldc, tA, tB, batch, bias, bias_mode, resid, ldr, sR, act, alpha, pre_out, dact):
+    """ops.gemm with pre_out / dact: True if the fast kernel ran, False -- nothing launched -- if it does not serve the product"""
+    if _BATCH_INVARIANT or batch != 1:
+        return False
+    h2_arm(A, B)
+    h2_mark_next(C)
+    call("tris_gemm_epilogue_next", P(pre_out), P(dact))
+
+    def launch():
+        return _declinable("tris_gemm_f32", P(A), P(B), P(C), M, N, K, lda, ldb, ldc, int(tA), int(tB), 1, 0, 0, 0, P(bias), bias_mode,
+                           P(resid), ldr, sR, act, float(alpha), None, 0, _stream())
+    return _timed("gemm", 2.0 * M * N * K, launch, nbytes=4.0 * (M * K + K * N + M * N * (2 + int(resid is not None))))
+
+
+def _gemm_padded(A, B, C, M, N, K, ldb, tB, bias, bias_mode, resid, act, alpha, use_ws):
+    """ops.gemm, batch-invariant, fewer than four rows: such products run a different (generic) kernel than larger ones, so they are
+    padded to four rows -- a sentence evaluated alone goes through the same arithmetic as one evaluated in a batch"""
+    A4 = A.new_zeros(4, K)
+    A4[:M].copy_(A.reshape(M, K))
+    R4 = None
+    if resid is not None:
+        R4 = resid.new_zeros(4, N)
+        R4[:M].copy_(resid.reshape(M, N))
+    C4 = C.new_empty(4, N)
+    gemm(A4, B, C4, 4, N, K, K, ldb, N, False, tB, bias=bias, bias_mode=bias_mode, resid=R4, ldr=N, act=act, alpha=alpha, use_ws=use_ws)
+    C.reshape(M, N).copy_(C4[:M])
+    return C
 
 
 def colsum(X, M, N, out):
@@ -630,13 +642,27 @@ def carry(src, dst):
     return dst
 
 
-def _launch_with_stats(y, M, N, launch):
-    import ctypes
-    part = torch.empty(((M + 127) // 128) * 2 * N, device=y.device, dtype=torch.float64)
-    rows = ctypes.c_int(0)
+def _part_rows(M, C, device):
+    """what the statistics / BatchNorm-backward epilogue of an [M, C] product writes: fp64 partial rows (two sums per channel and 128 rows)
+    and the word it leaves their number in (0: the entry point declined the shape, nothing was launched)"""
+    return torch.empty(((M + 127) // 128) * 2 * C, device=device, dtype=torch.float64), ctypes.c_int(0)
+
+
+def _launch_with_stats(y, M, N, launch, stats=True):
+    """launch(part, rows) writes y [M, N]; stats: and leaves the BatchNorm statistics of y as partial rows -> y._bn_part"""
+    if not stats:
+        return launch(None, None)
+    part, rows = _part_rows(M, N, y.device)
     launch(part, ctypes.byref(rows))
     if rows.value > 0:
         y._bn_part = _BnPart(part, rows.value)
+
+
+def _bn_bwd_bufs(M, C, device, pair=None):
+    """-> (part, rows, part2, dzw) of a data gradient that reduces for the BatchNorm behind it (_BnBwdLink): _part_rows, the rows of a paired
+    shortcut BatchNorm's third sum (pair: its `_bn_pair`) and, with operand planes, the amax word of the masked gradient"""
+    part, rows = _part_rows(M, C, device)
+    return part, rows, (torch.empty_like(part) if pair is not None else None), (_h2_slot() if planes_on() else None)
 
 
 def _declinable(name, *args):
@@ -795,7 +821,7 @@ def _a_planes(A, M, K):
         return A
     t = torch.empty_like(A)
     call("tris_h2_planes_f32", P(A), P(t), A.numel(), slot, _stream())
-    PL_STATS["converted"] = PL_STATS.get("converted", 0) + 1
+    PL_STATS["converted"] += 1
     return pl_tag(t, slot)
 
 
@@ -1049,7 +1075,7 @@ def h2_arm(A, B, a_slot=None, b_slot=None):
 # backward and the convolution backward that reads it, and the convolution weights exist as fp16 PIECE PLANES: float32 tensors in
 # torch's eyes whose bytes are the two fp16 pieces of every element, scaled by the power of two their amax word implies.  The tensor
 # carries `_pl = (step, word)`; only the ops below that say so accept one, everything else must see `unplanes(t)`.
-PL_STATS = {"unplanes": 0, "dx_planes": 0, "dy_planes": 0, "products": 0, "mixed": 0, "last": False, "last_t": False}
+PL_STATS = {"unplanes": 0, "dx_planes": 0, "dy_planes": 0, "products": 0, "mixed": 0, "converted": 0}
 
 
 _HAS_GPU = None
@@ -1211,38 +1237,40 @@ def pl_grad_in(dy):
     return dy
 
 
+# _Operands: what h2_pp hands the caller of a dense product -- the pointers of A and B to give the entry point, whether the product just
+# armed takes planes, and whether B (a 1x1 weight used as [k][n]) arrived as the planes of its TRANSPOSE: the product then runs with B as [n][k]
+_Operands = NamedTuple("_Operands", [("a", Optional[int]), ("b", Optional[int]), ("planes", bool), ("b_t", bool)])
+
+
 def h2_pp(A, B, a_slot=None, b_slot=None, y_planes=False, w_a=False, w_b=False, k_red=32, w_bt=False, y_mask=False):
-    """Arm the next dense product for h2 (as h2_arm) and return the pointers of its operands A, B to hand to the entry point.  With
+    """Arm the next dense product for h2 (as h2_arm) and return the _Operands to hand to the entry point.  With
     operand planes on: if one operand IS a plane tensor and the other one is too, or is a convolution weight (w_a / w_b: that
     operand is a parameter), the product runs on planes; a plane tensor next to an fp32 operand is rebuilt (counted in PL_STATS).
     k_red: the reduction length of the product -- the plane kernels (the fast kernels) need a multiple of 32; anything else (the weight
-    gradients of a 10 x 10 map at batch 2: 200 pixels) runs on the rebuilt tensors through the generic kernel."""
-    # w_bt: B is a 1x1 weight used as [k][n] (a data gradient): if its TRANSPOSED planes exist the caller gets those -- and must then
-    # run the product with B as [n][k] (PL_STATS["last_t"] says so)
-    PL_STATS["last"] = PL_STATS["last_t"] = False   # (did the product just armed take planes?  read by callers)
+    gradients of a 10 x 10 map at batch 2: 200 pixels) runs on the rebuilt tensors through the generic kernel.
+    w_bt: B is a 1x1 weight used as [k][n] (a data gradient): if its TRANSPOSED planes exist the caller gets those (_Operands.b_t)."""
     if A is None or B is None or a_slot is not None or b_slot is not None or not planes_on() or k_red % 32 != 0:
         if pl_word(A) is not None or pl_word(B) is not None:
             A, B = unplanes(A), unplanes(B)
         h2_arm(A, B, a_slot, b_slot)
-        return P(A), P(B)
+        return _Operands(P(A), P(B), False, False)
     wa, wb = pl_word(A), pl_word(B)
     if wa is not None or wb is not None:
         pa = (P(A), wa) if wa is not None else (_pl_weight(A) if w_a else None)
         pb = (P(B), wb) if wb is not None else (_pl_weight(B) if w_b else None)
+        b_t = False
         if w_bt and wb is None and pa is not None:
             tt = getattr(B, "_plwt", None)
             if tt is not None and tt[0] == _H2["step"]:
-                pb = (tt[1], tt[2])
-                PL_STATS["last_t"] = True
+                pb, b_t = (tt[1], tt[2]), True
         if pa is not None and pb is not None:
-            call("tris_h2_next_planes", pa[1], pb[1], (1 if y_planes else 0) | (2 if PL_STATS["last_t"] else 0) | (4 if y_mask else 0))
+            call("tris_h2_next_planes", pa[1], pb[1], (1 if y_planes else 0) | (2 if b_t else 0) | (4 if y_mask else 0))
             PL_STATS["products"] += 1
-            PL_STATS["last"] = True
-            return pa[0], pb[0]
+            return _Operands(pa[0], pb[0], True, b_t)
         PL_STATS["mixed"] += 1
         A, B = unplanes(A), unplanes(B)
     h2_arm(A, B)
-    return P(A), P(B)
+    return _Operands(P(A), P(B), False, False)
 
 
 class _BnBwdLink:
@@ -1289,16 +1317,140 @@ class _BnBwdLink:
         return _BnTaken(part, rows, dzw, part2)
 
 
+# ---- the steps of a Linear / 1x1 convolution and what the dense-product Functions share (LinearFn, LinearQGeluFn, Conv3x3Fn)
+# _LinOpts: what ops.linear tells LinearFn beyond the tensors autograd must see (one argument of apply).  act: 0 none | 1 ReLU | 2 QuickGELU
+# (forward-only); stats: leave the BatchNorm statistics of the output; grad_box / grad_box_out / grad_box_res (GradBox): where a later layer
+# left a gradient of x / where dx goes / where the residual's gradient goes; bn_link (_BnBwdLink), act_link (_ActLink): what x is the output of
+_LinOpts = NamedTuple("_LinOpts", [("act", int), ("stats", bool), ("grad_box", object), ("grad_box_out", object), ("grad_box_res", object),
+                                   ("bn_link", object), ("act_link", object)])
+
+
+def _bn_link_of(x):
+    """the `_bn_link` riding on x, if the consumer's data gradient may reduce for that BatchNorm"""
+    link = getattr(x, "_bn_link", None)
+    return link if (link is not None and torch.is_grad_enabled() and x.requires_grad and cfg.bn_bwd_fuse) else None
+
+
+def _lin_fwd_stats(x, w, y, M, N, K, part, rows):
+    def launch():
+        pp = h2_pp(x, w, w_b=True, k_red=K)
+        call("tris_gemm_bnstat_f32", pp.a, pp.b, P(y), M, N, K, part.data_ptr(), rows, _stream())
+    _timed("gemm", 2.0 * M * N * K, launch, nbytes=4.0 * (M * K + K * N + M * N), tag=_shape_tag(f"bnstat M{M} N{N} K{K}"))
+
+
+def _grad_forms(dy, x, x_pl, fp32_dy, planes_x=False):
+    """-> dy, x: the gradient a product's backward is handed and the input it saved (plane tag x_pl) in the forms its kernels read: dy fp32 if
+    fp32_dy (or, planes_x, if x is no plane tensor); a plane x next to an fp32 dy rebuilt (vis_project: the weight gradient reads that)"""
+    dy = pl_grad_in(dy.contiguous())
+    _retag(x, x_pl)
+    if pl_word(dy) is not None and (fp32_dy or (planes_x and pl_word(x) is None)):
+        dy = unplanes(dy)
+    if pl_word(dy) is None:
+        x = unplanes(x)
+    return dy, x
+
+
+def _lin_resid_grad(dy, box, needed, wgrad_reads_dy):
+    """the gradient of a residual added in the forward's epilogue: dy itself; None if not needed or taken over by `box`"""
+    if not needed:
+        return None
+    if box is not None and box.deposit(dy):
+        return None    # picked up by the block's LayerNorm backward (read-only there: no copy needed)
+    if _wgrad_enabled() and wgrad_reads_dy:
+        # dy is about to be read by the weight-gradient stream; autograd may accumulate IN PLACE into a gradient
+        # tensor it is handed back (InputBuffer steals sole-owner tensors), so the residual branch gets its own copy
+        return dy.clone()
+    return dy
+
+
+def _box_take(box):
+    """empty the GradBox of a product's input -> (extra, pool): a residual-branch gradient left by a later layer of the same block, to
+    be added in the data gradient's epilogue, and (H, W) if it is given as the gradient of its 2x2 average pool (GradBox.pool)"""
+    extra = pool = None
+    if box is not None:
+        box.consumed = True
+        if box.value is not None:
+            extra, pool, box.value, box.pool = box.value, box.pool, None, None
+    return extra, pool
+
+
+def _lin_dgrad_bnbwd(dy, x, w, dx, dims, link, extra, pool):
+    """dx = mask(dy . W + extra) with the sums of the BatchNorm backward behind x as partial rows (tris_gemm_bnbwd_f32), the link filled.
+    -> False, nothing launched, where the form does not apply or the entry point declines the shape"""
+    M, N, K = dims
+    ypl = link.from_y and pl_word(x) is not None   # (the BatchNorm's output as planes: only a plane product masks from it)
+    if ypl and pl_word(dy) is None:
+        return False
+    pr2 = link.pair if (cfg.bn_pair and "bwd" in cfg.bn_pair_parts and planes_on()) else None
+    part, rows, part2, dzw = _bn_bwd_bufs(M, K, x.device, pr2)     # (part2: the shortcut BatchNorm's sum(dz * xhat_s), same rows)
+    bits = ypl and link.mask is not None
+
+    def launch():
+        pp = h2_pp(dy, w, w_b=True, y_planes=ypl, k_red=N, w_bt=True, y_mask=bits)
+        if dzw is not None:
+            call("tris_amax_next", dzw)
+        by = (P(x) if (pp.planes or not ypl) else P(unplanes(x))) if link.from_y else None
+        if bits and pp.planes:
+            by = link.mask.data_ptr()       # (the product took planes and was armed with flag 4: bn_y is the byte mask)
+        if pool is not None:
+            call("tris_gemm_resid_pool_next", pool[0], pool[1])
+        if part2 is not None:
+            call("tris_gemm_bnbwd_x2_next", P(pr2.x), P(pr2.mean), P(pr2.invstd), part2.data_ptr())
+        call("tris_gemm_bnbwd_f32", pp.a, pp.b, P(dx), M, K, N, P(extra), K, P(link.x), by,
+             P(link.mean), P(link.invstd), P(link.gamma), P(link.beta), part.data_ptr(), ctypes.byref(rows), _stream())
+        return rows.value > 0     # (False: the entry point declined the shape, nothing was launched)
+    ran = _timed("gemm_bnbwd", 2.0 * M * N * K, launch, tag=_shape_tag(f"M{M} N{K} K{N}"),
+                 nbytes=4.0 * (M * N + N * K + M * K * (2 + int(link.from_y) + int(extra is not None))))
+    if ran:
+        link.fill(dx, part, rows.value, dzw, part2)
+    return ran
+
+
+def _lin_dgrad(dy, x, w, dx, dims, link, alink, box, extra, pool):
+    """dx = dy . W (+ extra) in the first of four forms that applies -> "bnbwd" | "qgelu" | "pool" | "plain", the one that ran"""
+    M, N, K = dims
+    # x is the output of a BatchNorm(+ReLU) that has no other consumer: mask dx and reduce it for that BatchNorm's backward in this
+    # product's epilogue (_BnBwdLink).  With a gradient box whose value has NOT arrived yet (the other consumer's backward is still to
+    # run and will hand its term to autograd) the sums would miss that term: the plain data gradient runs and the BatchNorm backward
+    # does its own reduction
+    if link is not None and (box is None or extra is not None) and _lin_dgrad_bnbwd(dy, x, w, dx, dims, link, extra, pool):
+        return "bnbwd"
+    # x = QuickGELU(pre) with this product as its only consumer (linear_qgelu): the data gradient comes out of the epilogue already
+    # multiplied by quickgelu'(pre); the producer's backward is told so
+    if alink is not None and extra is None and gemm(dy, w, dx, M, K, N, N, K, K, False, False, dact=alink.pre) is not False:
+        alink.applied = True
+        return "qgelu"
+    if pool is not None:
+        if gemm(dy, w, dx, M, K, N, N, K, K, False, False, resid=extra, ldr=K, w_b=True, w_bt=True, resid_pool=pool) is not False:
+            return "pool"
+        extra = _avgpool2_bwd(extra, x.shape)    # (a product the fast kernel does not serve: the expansion after all)
+    gemm(dy, w, dx, M, K, N, N, K, K, False, False, resid=extra, ldr=K, w_b=True, w_bt=True)
+    return "plain"
+
+
+def _wgrad(p, make, needs, *reads):
+    """The weight gradient of a product, make(out) launching it: into p's sink on the weight-gradient stream (-> None; reads: every tensor
+    the launch reads), else as _emit hands it to autograd."""
+    sk = _sink(p) if needs else None
+    if sk is None:
+        return _emit(p, make, needs)
+    on_wgrad_stream(lambda: make(sk), *reads, sink=sk)
+    return None
+
+
+def _bias_grad(p, dy, M, N, needs):
+    """the gradient of a bias added to the rows of an [M, N] product: the column sum of dy (p None: there was no bias)"""
+    return None if p is None else _emit(p, lambda o: colsum(dy, M, N, o), needs, reads=(dy,))
+
+
 class LinearFn(torch.autograd.Function):
     """y = act(x . W^T + b) + resid  with W [N, K] (nn.Linear) or [N, K, 1, 1] (1x1 conv on channels-last)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, resid, act, stats=False, grad_box=None, grad_box_out=None, grad_box_res=None, bn_link=None,
-                act_link=None):
+    def forward(ctx, x, w, b, resid, o):
         _chk(x, w, b, resid)
-        ctx.grad_box, ctx.grad_box_out, ctx.grad_box_res = grad_box, grad_box_out, grad_box_res
-        ctx.act_link = act_link
-        ctx.bn_link = bn_link if (bn_link is not None and x.is_contiguous() and bn_link.x.shape == x.shape) else None
+        ctx.opts = o
+        ctx.bn_link = o.bn_link if (o.bn_link is not None and x.is_contiguous() and o.bn_link.x.shape == x.shape) else None
         x = x.contiguous()
         K = x.shape[-1]
         N = w.numel() // K
@@ -1306,131 +1458,49 @@ class LinearFn(torch.autograd.Function):
         y = torch.empty(*x.shape[:-1], N, device=x.device, dtype=torch.float32)
         if resid is not None:
             resid = resid.contiguous()
-        want_stats = stats and b is None and resid is None and act == 0
-        if want_stats:
-            _launch_with_stats(y, M, N, lambda part, rows: _timed(
-                "gemm", 2.0 * M * N * K, lambda: (lambda pp: call("tris_gemm_bnstat_f32", pp[0], pp[1], P(y), M, N, K,
-                                                                  part.data_ptr(), rows, _stream()))(h2_pp(x, w, w_b=True, k_red=K)),
-                nbytes=4.0 * (M * K + K * N + M * N), tag=_shape_tag(f"bnstat M{M} N{N} K{K}")))
+        if o.stats and b is None and resid is None and o.act == 0:
+            _launch_with_stats(y, M, N, lambda part, rows: _lin_fwd_stats(x, w, y, M, N, K, part, rows))
         else:
             gemm(x, w, y, M, N, K, K, K, N, False, True, bias=b, bias_mode=1 if b is not None else 0, resid=resid,
-                 ldr=N, act=act, w_b=True)
-        ctx.act, ctx.dims = act, (M, N, K)
+                 ldr=N, act=o.act, w_b=True)
+        ctx.dims, ctx.params, ctx.x_pl = (M, N, K), (w, b), getattr(x, "_pl", None)
         ctx.has_b, ctx.has_r = b is not None, resid is not None
-        ctx.params = (w, b)
-        ctx.x_pl = getattr(x, "_pl", None)
-        ctx.save_for_backward(x, w, b, y if act == 1 else None)
+        ctx.save_for_backward(x, w, b, y if o.act == 1 else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.act == 2:
+        o, needs = ctx.opts, ctx.needs_input_grad
+        if o.act == 2:
             raise RuntimeError("fused QuickGELU epilogue is forward-only; use QGeluFn when gradients are needed")
-        if ctx.act == 1 and ctx.has_r:
+        if o.act == 1 and ctx.has_r:
             raise RuntimeError("relu + residual epilogue is forward-only")
         x, w, b, y = ctx.saved_tensors
-        pw, pb = ctx.params
-        M, N, K = ctx.dims
-        dy = pl_grad_in(dy.contiguous())
-        _retag(x, ctx.x_pl)
-        if pl_word(dy) is not None and (ctx.has_r or ctx.has_b or ctx.act == 1):
-            dy = unplanes(dy)      # (bias / residual / ReLU backward read the gradient element-wise: never on the trunk's path)
-        if pl_word(dy) is None:
-            x = unplanes(x)        # (a plane input next to an fp32 gradient -- vis_project: the weight gradient reads the rebuilt tensor)
-        d_res = dy if ctx.has_r and ctx.needs_input_grad[3] else None
-        if d_res is not None and ctx.grad_box_res is not None and ctx.grad_box_res.deposit(d_res):
-            d_res = None   # picked up by the block's LayerNorm backward (read-only there: no copy needed)
-        if d_res is not None and _wgrad_enabled() and ctx.needs_input_grad[1]:
-            # dy is about to be read by the weight-gradient stream; autograd may accumulate IN PLACE into a gradient
-            # tensor it is handed back (InputBuffer steals sole-owner tensors), so the residual branch gets its own copy
-            d_res = dy.clone()
-        if ctx.act == 1:
+        (pw, pb), (M, N, K) = ctx.params, ctx.dims
+        # (bias / residual / ReLU backward read the gradient element-wise: never on the trunk's path)
+        dy, x = _grad_forms(dy, x, ctx.x_pl, ctx.has_r or ctx.has_b or o.act == 1)
+        d_res = _lin_resid_grad(dy, o.grad_box_res, ctx.has_r and needs[3], needs[1])
+        if o.act == 1:
             dy = ew("TRIS_EW_RELU_BWD", dy, y)
+        extra, pool = _box_take(o.grad_box)
         dx = None
-        box = ctx.grad_box
-        extra = None   # a residual-branch gradient left by a later layer of the same block: added in the GEMM epilogue
-        pool = None    # ... given as the gradient of its 2x2 average pool (GradBox.pool)
-        if box is not None:
-            box.consumed = True
-            if box.value is not None:
-                extra, box.value = box.value, None
-                pool, box.pool = box.pool, None
-        if ctx.needs_input_grad[0]:
+        if needs[0]:
             dx = torch.empty_like(x)
-            link, fused = ctx.bn_link, False
-            if link is not None and (box is None or extra is not None):
-                # x is the output of a BatchNorm(+ReLU) that has no other consumer: mask dx and reduce it for that BatchNorm's
-                # backward in this product's epilogue (_BnBwdLink).  With a gradient box whose value has NOT arrived yet (the
-                # other consumer's backward is still to run and will hand its term to autograd) the sums would miss that term:
-                # the plain data gradient runs and the BatchNorm backward does its own reduction
-                import ctypes
-                part = torch.empty(((M + 127) // 128) * 2 * K, device=x.device, dtype=torch.float64)
-                rows = ctypes.c_int(0)
-                ypl = link.from_y and pl_word(x) is not None   # (the BatchNorm's output as planes: only a plane product masks from it)
-                pr2 = link.pair if (cfg.bn_pair and "bwd" in cfg.bn_pair_parts and planes_on()) else None
-                part2 = None
-                if not ypl or pl_word(dy) is not None:
-                    if pr2 is not None:
-                        part2 = torch.empty_like(part)     # (the shortcut BatchNorm's sum(dz * xhat_s), same rows)
-                    dzw = _h2_slot() if planes_on() else None   # (the masked gradient's amax: the bound of that BatchNorm's dx)
-
-                    def launch():
-                        bits = ypl and link.mask is not None
-                        pp = h2_pp(dy, w, w_b=True, y_planes=ypl, k_red=N, w_bt=True, y_mask=bits)
-                        if dzw is not None:
-                            call("tris_amax_next", dzw)
-                        by = (P(x) if (PL_STATS["last"] or not ypl) else P(unplanes(x))) if link.from_y else None
-                        if bits and PL_STATS["last"]:
-                            by = link.mask.data_ptr()       # (the product took planes and was armed with flag 4: bn_y is the byte mask)
-                        if pool is not None:
-                            call("tris_gemm_resid_pool_next", pool[0], pool[1])
-                        if part2 is not None:
-                            call("tris_gemm_bnbwd_x2_next", P(pr2.x), P(pr2.mean), P(pr2.invstd), part2.data_ptr())
-                        call("tris_gemm_bnbwd_f32", pp[0], pp[1], P(dx), M, K, N, P(extra), K, P(link.x), by,
-                             P(link.mean), P(link.invstd), P(link.gamma), P(link.beta), part.data_ptr(), ctypes.byref(rows), _stream())
-                        return rows.value > 0     # (False: the entry point declined the shape, nothing was launched)
-                    _timed("gemm_bnbwd", 2.0 * M * N * K, launch, tag=_shape_tag(f"M{M} N{K} K{N}"),
-                           nbytes=4.0 * (M * N + N * K + M * K * (2 + int(link.from_y) + int(extra is not None))))
-                    if rows.value > 0:
-                        fused = True
-                        link.fill(dx, part, rows.value, dzw, part2)
-            alink = ctx.act_link
-            if not fused and alink is not None and extra is None:
-                # x = QuickGELU(pre) with this product as its only consumer (linear_qgelu): the data gradient comes out of the
-                # epilogue already multiplied by quickgelu'(pre); the producer's backward is told so
-                if gemm(dy, w, dx, M, K, N, N, K, K, False, False, dact=alink.pre) is not False:
-                    fused = alink.applied = True
-            if not fused and pool is not None:
-                if gemm(dy, w, dx, M, K, N, N, K, K, False, False, resid=extra, ldr=K, w_b=True, w_bt=True, resid_pool=pool) is False:
-                    extra = _avgpool2_bwd(extra, x.shape)    # (a product the fast kernel does not serve: the expansion after all)
-                else:
-                    fused = True
-            if not fused:
-                gemm(dy, w, dx, M, K, N, N, K, K, False, False, resid=extra, ldr=K, w_b=True, w_bt=True)
+            _lin_dgrad(dy, x, w, dx, ctx.dims, ctx.bn_link, o.act_link, o.grad_box, extra, pool)
         elif extra is not None:
             raise RuntimeError("a residual gradient was handed to a layer whose input needs no gradient")
-        if dx is not None and ctx.grad_box_out is not None and ctx.grad_box_out.deposit(dx):
+        if dx is not None and o.grad_box_out is not None and o.grad_box_out.deposit(dx):
             dx = None   # the block's first conv adds it in its data-gradient epilogue
-        dw = None
-        if ctx.needs_input_grad[1]:
-            if _sink(pw) is not None:   # into the gradient arena, on the weight-gradient stream
-                on_wgrad_stream(lambda: gemm(dy, x, _sink(pw), N, K, M, N, K, K, True, False, mark=False), dy, x, sink=_sink(pw))
-            else:
-                dw = _emit(pw, lambda o: gemm(dy, x, o, N, K, M, N, K, K, True, False, mark=False), True)
-        db = None
-        if ctx.has_b:
-            db = _emit(pb, lambda o: colsum(dy, M, N, o), ctx.needs_input_grad[2], reads=(dy,))
-        return dx, dw, db, d_res, None, None, None, None, None, None, None
+        dw = _wgrad(pw, lambda out: gemm(dy, x, out, N, K, M, N, K, K, True, False, mark=False), needs[1], dy, x)
+        db = _bias_grad(pb, dy, M, N, needs[2])
+        return dx, dw, db, d_res, None
 
 
 def linear(x, w, b=None, resid=None, act=0, stats=False, grad_box=None, grad_box_out=None, grad_box_res=None, act_link=False):
     """act_link=True: x is the output of linear_qgelu and THIS product is its only consumer -- the QuickGELU backward rides this
     product's data-gradient epilogue (the caller vouches for the single consumer)"""
-    link = getattr(x, "_bn_link", None)
-    if link is not None and not (torch.is_grad_enabled() and x.requires_grad and cfg.bn_bwd_fuse):
-        link = None
     alink = getattr(x, "_act_link", None) if (act_link and torch.is_grad_enabled() and x.requires_grad) else None
-    return LinearFn.apply(x, w, b, resid, act, stats, grad_box, grad_box_out, grad_box_res, link, alink)
+    return LinearFn.apply(x, w, b, resid, _LinOpts(act, stats, grad_box, grad_box_out, grad_box_res, _bn_link_of(x), alink))
 
 
 class _ActLink:
@@ -1458,7 +1528,7 @@ class LinearQGeluFn(torch.autograd.Function):
         if gemm(x, w, y, M, N, K, K, K, N, False, True, bias=b, bias_mode=1 if b is not None else 0, act=2, pre_out=pre) is False:
             gemm(x, w, pre, M, N, K, K, K, N, False, True, bias=b, bias_mode=1 if b is not None else 0)
             ew("TRIS_EW_QGELU", pre, out=y)
-        ctx.dims, ctx.has_b, ctx.params = (M, N, K), b is not None, (w, b)
+        ctx.dims, ctx.params = (M, N, K), (w, b)
         ctx.link = y._act_link = _ActLink(pre)
         ctx.save_for_backward(x, w, pre)
         return y
@@ -1466,23 +1536,15 @@ class LinearQGeluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, pre = ctx.saved_tensors
-        pw, pb = ctx.params
-        M, N, K = ctx.dims
+        (pw, pb), (M, N, K) = ctx.params, ctx.dims
         dy = dy.contiguous()
         dpre = dy if ctx.link.applied else ew("TRIS_EW_QGELU_BWD", dy, pre)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             gemm(dpre, w, dx, M, K, N, N, K, K, False, False)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            if _sink(pw) is not None:
-                on_wgrad_stream(lambda: gemm(dpre, x, _sink(pw), N, K, M, N, K, K, True, False, mark=False), dpre, x, sink=_sink(pw))
-            else:
-                dw = _emit(pw, lambda o: gemm(dpre, x, o, N, K, M, N, K, K, True, False, mark=False), True)
-        db = None
-        if ctx.has_b:
-            db = _emit(pb, lambda o: colsum(dpre, M, N, o), ctx.needs_input_grad[2], reads=(dpre,))
+        dw = _wgrad(pw, lambda out: gemm(dpre, x, out, N, K, M, N, K, K, True, False, mark=False), ctx.needs_input_grad[1], dpre, x)
+        db = _bias_grad(pb, dpre, M, N, ctx.needs_input_grad[2])
         return dx, dw, db
 
 
@@ -1581,142 +1643,140 @@ def bmm(A, B, tB=False, alpha=1.0):
 
 
 # ----------------------------------------------------------------------------------------------- 3x3 conv
+# _ConvOpts: what ops.conv3x3 tells Conv3x3Fn beyond the tensors autograd must see (one argument of apply).
+# bn_link: x is the output of a BatchNorm + ReLU with no other consumer (_BnBwdLink): the data gradient reduces that BatchNorm's backward
+# sums in its epilogue.  lazy (_BnLazy): `x` is the NOT-YET-WRITTEN output buffer of a BatchNorm + ReLU over lazy.x
+# (batch_norm(..., lazy=True)); the direct kernels normalise x_raw while they stage it and `x` is never written -- or, when they cannot
+# serve the shape after all, it is written first and everything proceeds as usual.  (h2: the unwritten buffer carries the amax word of
+# an upper bound of its would-be contents, BatchNormFn.forward.)
+_ConvOpts = NamedTuple("_ConvOpts", [("stride", int), ("stats", bool), ("lazy", Optional[_BnLazy]), ("bn_link", object)])
+
+
+def _conv_pp(a, w_param, w_cl):
+    """_Operands of a 3x3 product (activation or gradient `a`, weight parameter `w_param` whose kernel layout is `w_cl`)"""
+    pp = h2_pp(a, w_param, w_b=True)
+    return pp if pp.b != P(w_param) else pp._replace(b=P(w_cl))
+
+
+def _conv_fwd(x, w_param, w, stride, stats, lazy=None):
+    """y = conv3x3(x), stats: with the BatchNorm statistics of y.  lazy: x is unwritten -- y = conv3x3(relu(bn(lazy.x))), the BatchNorm
+    folded into the direct kernel's staging (stride 1, conv3x3_bnin_ok)"""
+    B, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+    y = torch.empty(B, Ho, Wo, Cout, device=x.device, dtype=torch.float32)
+
+    def launch(part, rows):
+        def run():
+            if lazy is not None:
+                if lazy.bound is not None:      # (None outside h2)
+                    h2_arm(None, w_param, a_slot=lazy.bound)
+                return call("tris_conv3x3_fwd_bnin_f32", P(lazy.x), P(lazy.mean), P(lazy.invstd), P(lazy.gamma), P(lazy.beta), P(w), P(y),
+                            B, H, W, Cin, Cout, None if part is None else part.data_ptr(), rows, _stream())
+            pp = _conv_pp(x, w_param, w)
+            if part is None:
+                call("tris_conv3x3_fwd_f32", pp.a, pp.b, P(y), B, H, W, Cin, Cout, stride, _stream())
+            else:
+                call("tris_conv3x3_fwd_bnstat_f32", pp.a, pp.b, P(y), B, H, W, Cin, Cout, stride, part.data_ptr(), rows, _stream())
+        form = "bnin " if lazy is not None else ("" if part is None else "bnstat ")
+        _timed("conv3x3_fwd", 2.0 * B * Ho * Wo * Cout * 9 * Cin, run, nbytes=4.0 * (B * H * W * Cin + B * Ho * Wo * Cout + 9 * Cin * Cout),
+               tag=_shape_tag(f"{form}B{B} {H}x{W} {Cin}->{Cout}" + ("" if lazy is not None else f" s{stride}")))
+    _launch_with_stats(y, B * Ho * Wo, Cout, launch, stats)
+    return y
+
+
+def _conv_dgrad(dy, w_param, w, dx, link):
+    """dx = the data gradient of a stride-1 conv3x3.  link (_BnBwdLink or None): masked and reduced for the BatchNorm + ReLU behind x in the
+    epilogue (as _lin_dgrad_bnbwd) and the link filled -- unless the entry point declines the shape: then the plain form, as without a link"""
+    B, H, W, Cin = dx.shape
+    Cout = w.shape[0]
+    fl, tag = 2.0 * B * H * W * Cout * 9 * Cin, _shape_tag(f"B{B} {H}x{W} {Cin}<-{Cout}")
+    if link is not None:
+        part, rows, _, dzw = _bn_bwd_bufs(B * H * W, Cin, dx.device)
+
+        def fused():
+            pp = _conv_pp(dy, w_param, w)
+            if dzw is not None:
+                call("tris_amax_next", dzw)
+            call("tris_conv3x3_dgrad_bnbwd_f32", pp.a, pp.b, P(dx), B, H, W, Cin, Cout, P(link.x), P(link.mean), P(link.invstd),
+                 P(link.gamma), P(link.beta), part.data_ptr(), ctypes.byref(rows), _stream())
+            return rows.value > 0
+        if _timed("conv3x3_dgrad_bnbwd", fl, fused, tag=tag, nbytes=4.0 * (B * H * W * (Cout + 2 * Cin) + 9 * Cin * Cout)):
+            link.fill(dx, part, rows.value, dzw)
+            return
+
+    def plain():
+        pp = _conv_pp(dy, w_param, w)
+        call("tris_conv3x3_dgrad_f32", pp.a, pp.b, P(dx), B, H, W, Cin, Cout, _stream())
+    _timed("conv3x3_dgrad", fl, plain, tag=tag, nbytes=4.0 * (B * H * W * (Cout + Cin) + 9 * Cin * Cout))
+
+
+def _conv_wgrad(dy, x, o, stride, bn=(), h2_in=None):
+    """the weight gradient into o [Cout, 3, 3, Cin].  bn = (mean, invstd, gamma, beta): x is the raw input of a BatchNorm + ReLU folded
+    into the forward (h2_in: the amax word of its would-be output) -- folded here as well, or materialised after all"""
+    B, H, W, Cin = x.shape
+    Cout = o.shape[0]
+    ws = workspace(0)
+    fl = 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * Cout * 9 * Cin
+    nb = 4.0 * (B * H * W * Cin + dy.numel() + 9 * Cin * Cout)
+    if bn and conv3x3_bnin_ok(x.shape, Cout):
+        mean, invstd, gamma, beta = bn
+
+        def folded():
+            if h2_in is not None:
+                h2_arm(dy, None, b_slot=h2_in)
+            call("tris_conv3x3_wgrad_bnin_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(dy), P(o), B, H, W, Cin, Cout,
+                 P(ws), ws.numel() * 4, _stream())
+        return _timed("conv3x3_wgrad", fl, folded, nbytes=nb, tag=_shape_tag(f"bnin B{B} {H}x{W} {Cin}->{Cout}"))
+    xin = _bn_write(x, *bn, torch.empty_like(x), True) if bn else x    # (materialise relu(bn(x)) after all)
+
+    def plain():
+        pp = h2_pp(dy, xin, k_red=dy.shape[0] * dy.shape[1] * dy.shape[2])
+        call("tris_conv3x3_wgrad_f32", pp.b, pp.a, P(o), B, H, W, Cin, Cout, stride, P(ws), ws.numel() * 4, _stream())
+    return _timed("conv3x3_wgrad", fl, plain, nbytes=nb, tag=_shape_tag(f"B{B} {H}x{W} {Cin}->{Cout} s{stride}"))
+
+
 class Conv3x3Fn(torch.autograd.Function):
     """x [B,H,W,Cin] channels-last, w [Cout,Cin,3,3] in channels_last memory, pad 1, stride 1|2."""
 
     @staticmethod
-    def forward(ctx, x, w, stride, stats=False, lazy=None, bn_link=None):
-        """bn_link: x is the output of a BatchNorm + ReLU with no other consumer (_BnBwdLink): the data gradient reduces that
-        BatchNorm's backward sums in its epilogue.
-        lazy (_BnLazy): `x` is the NOT-YET-WRITTEN output buffer of a BatchNorm + ReLU over lazy.x
-        (batch_norm(..., lazy=True)); the direct kernels normalise x_raw while they stage it and `x` is never written -- or, when
-        they cannot serve the shape after all, it is written here first and everything proceeds as usual.  (h2: the unwritten
-        buffer carries the amax word of an upper bound of its would-be contents, BatchNormFn.forward.)"""
+    def forward(ctx, x, w, o):
         _chk(x, w)
-        ctx.bn_link = bn_link if (bn_link is not None and stride == 1 and not bn_link.from_y and x.is_contiguous()
-                                  and bn_link.x.shape == x.shape) else None
+        link, lazy = o.bn_link, o.lazy
+        ctx.bn_link = link if (link is not None and o.stride == 1 and not link.from_y and x.is_contiguous() and link.x.shape == x.shape) else None
         x = x.contiguous()
         ctx.params = (w,)
         w = cl_weight(w)
-        B, H, W, Cin = x.shape
-        Cout = w.shape[0]
-        ctx.lazy = None
-        ctx.stride = stride
+        ctx.stride, ctx.h2_in = o.stride, None
+        ctx.lazy = lazy is not None and o.stride == 1 and conv3x3_bnin_ok(x.shape, w.shape[0])
+        if ctx.lazy:
+            ctx.h2_in = lazy.bound
+            ctx.save_for_backward(lazy.x, w, lazy.mean, lazy.invstd, lazy.gamma, lazy.beta)
+            return _conv_fwd(x, ctx.params[0], w, 1, o.stats, lazy)
         if lazy is not None:
-            if stride == 1 and conv3x3_bnin_ok(x.shape, Cout):
-                y = torch.empty(B, H, W, Cout, device=x.device, dtype=torch.float32)
-                fl = 2.0 * B * H * W * Cout * 9 * Cin
-                nb = 4.0 * (B * H * W * (Cin + Cout) + 9 * Cin * Cout)
-                ctx.h2_in = bound = lazy.bound      # (None outside h2)
-
-                def launch(part, rows):
-                    return _timed("conv3x3_fwd", fl, lambda: (bound is not None and h2_arm(None, ctx.params[0], a_slot=bound), call(
-                        "tris_conv3x3_fwd_bnin_f32", P(lazy.x), P(lazy.mean), P(lazy.invstd), P(lazy.gamma), P(lazy.beta), P(w), P(y),
-                        B, H, W, Cin, Cout, None if part is None else part.data_ptr(), rows, _stream()))[1], nbytes=nb,
-                        tag=_shape_tag(f"bnin B{B} {H}x{W} {Cin}->{Cout}"))
-                if stats:
-                    _launch_with_stats(y, B * H * W, Cout, launch)
-                else:
-                    launch(None, None)
-                ctx.lazy = True
-                ctx.save_for_backward(lazy.x, w, lazy.mean, lazy.invstd, lazy.gamma, lazy.beta)
-                return y
             _bn_write(lazy.x, lazy.mean, lazy.invstd, lazy.gamma, lazy.beta, x, True)
-        if pl_word(x) is not None and (Cin % 32 != 0 or stride != 1):
+        if pl_word(x) is not None and (x.shape[3] % 32 != 0 or o.stride != 1):
             x = unplanes(x)        # (the fast kernels' gather needs 32-channel pieces; the stem's strided first convolution reads the image)
         ctx.x_pl = getattr(x, "_pl", None)
-        Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
-        y = torch.empty(B, Ho, Wo, Cout, device=x.device, dtype=torch.float32)
-        fl = 2.0 * B * Ho * Wo * Cout * 9 * Cin
-        nb = 4.0 * (B * H * W * Cin + B * Ho * Wo * Cout + 9 * Cin * Cout)
-        if stats:
-            _launch_with_stats(y, B * Ho * Wo, Cout, lambda part, rows: _timed(
-                "conv3x3_fwd", fl, lambda: (lambda pp: call("tris_conv3x3_fwd_bnstat_f32", pp[0], pp[1], P(y), B, H, W, Cin, Cout,
-                                                            stride, part.data_ptr(), rows, _stream()))(_conv_pp(x, ctx.params[0], w)),
-                nbytes=nb, tag=_shape_tag(f"bnstat B{B} {H}x{W} {Cin}->{Cout} s{stride}")))
-        else:
-            _timed("conv3x3_fwd", fl,
-                   lambda: (lambda pp: call("tris_conv3x3_fwd_f32", pp[0], pp[1], P(y), B, H, W, Cin, Cout, stride, _stream()))(
-                       _conv_pp(x, ctx.params[0], w)), nbytes=nb, tag=_shape_tag(f"B{B} {H}x{W} {Cin}->{Cout} s{stride}"))
         ctx.save_for_backward(x, w)
-        return y
+        return _conv_fwd(x, ctx.params[0], w, o.stride, o.stats)
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.lazy:
-            x, w, mean, invstd, gamma, beta = ctx.saved_tensors   # x = the BatchNorm's raw input
-        else:
-            x, w = ctx.saved_tensors
-        B, H, W, Cin = x.shape
-        Cout = w.shape[0]
-        dy = pl_grad_in(dy.contiguous())
-        if not ctx.lazy:
-            _retag(x, ctx.x_pl)
-        if pl_word(dy) is not None and (ctx.lazy or pl_word(x) is None or Cout % 32 != 0):
-            dy = unplanes(dy)      # (the BatchNorm-folded forms and the stem's first convolution read fp32)
-        if pl_word(dy) is None:
-            x = unplanes(x)
+        x, w, *bn = ctx.saved_tensors      # (lazy: x is the raw input of the folded BatchNorm, bn its mean, invstd, gamma, beta)
+        wp = ctx.params[0]
+        # (the BatchNorm-folded forms and the stem's first convolution read an fp32 gradient)
+        dy, x = _grad_forms(dy, x, None if ctx.lazy else ctx.x_pl, ctx.lazy or w.shape[0] % 32 != 0, planes_x=True)
         dx = None
         if ctx.needs_input_grad[0]:
             if ctx.stride != 1:
                 raise NotImplementedError("dgrad of the strided stem conv is never needed (its input is the image)")
             dx = torch.empty_like(x)
-            fl = 2.0 * B * H * W * Cout * 9 * Cin
-            link, fused = ctx.bn_link, False
-            if link is not None:   # (see LinearFn.backward)
-                import ctypes
-                part = torch.empty(((B * H * W + 127) // 128) * 2 * Cin, device=x.device, dtype=torch.float64)
-                rows = ctypes.c_int(0)
-                dzw = _h2_slot() if planes_on() else None   # (the masked gradient's amax: the bound of that BatchNorm's dx)
-
-                def launch():
-                    pp = _conv_pp(dy, ctx.params[0], w)
-                    if dzw is not None:
-                        call("tris_amax_next", dzw)
-                    call("tris_conv3x3_dgrad_bnbwd_f32", pp[0], pp[1], P(dx), B, H, W, Cin, Cout, P(link.x), P(link.mean), P(link.invstd),
-                         P(link.gamma), P(link.beta), part.data_ptr(), ctypes.byref(rows), _stream())
-                    return rows.value > 0
-                _timed("conv3x3_dgrad_bnbwd", fl, launch, tag=_shape_tag(f"B{B} {H}x{W} {Cin}<-{Cout}"), nbytes=4.0 * (B * H * W * (Cout + 2 * Cin) + 9 * Cin * Cout))
-                if rows.value > 0:
-                    fused = True
-                    link.fill(dx, part, rows.value, dzw)
-            if not fused:
-                _timed("conv3x3_dgrad", fl,
-                       lambda: (lambda pp: call("tris_conv3x3_dgrad_f32", pp[0], pp[1], P(dx), B, H, W, Cin, Cout, _stream()))(
-                           _conv_pp(dy, ctx.params[0], w)), tag=_shape_tag(f"B{B} {H}x{W} {Cin}<-{Cout}"),
-                       nbytes=4.0 * (B * H * W * (Cout + Cin) + 9 * Cin * Cout))
-
-        def wgrad(o):
-            ws = workspace(0)
-            fl = 2.0 * dy.shape[0] * dy.shape[1] * dy.shape[2] * Cout * 9 * Cin
-            nb = 4.0 * (B * H * W * Cin + dy.numel() + 9 * Cin * Cout)
-            xin = x
-            if ctx.lazy:
-                if conv3x3_bnin_ok(x.shape, Cout):
-                    return _timed("conv3x3_wgrad", fl, lambda: (ctx.h2_in is not None and h2_arm(dy, None, b_slot=ctx.h2_in), call(
-                        "tris_conv3x3_wgrad_bnin_f32", P(x), P(mean), P(invstd), P(gamma), P(beta), P(dy), P(o), B, H, W, Cin,
-                        Cout, P(ws), ws.numel() * 4, _stream()))[1], nbytes=nb, tag=_shape_tag(f"bnin B{B} {H}x{W} {Cin}->{Cout}"))
-                xin = _bn_write(x, mean, invstd, gamma, beta, torch.empty_like(x), True)   # materialise relu(bn(x)) after all
-            return _timed("conv3x3_wgrad", fl, lambda: (lambda pp: call(
-                "tris_conv3x3_wgrad_f32", pp[1], pp[0], P(o), B, H, W, Cin, Cout, ctx.stride, P(ws), ws.numel() * 4, _stream()))(
-                    h2_pp(dy, xin, k_red=dy.shape[0] * dy.shape[1] * dy.shape[2])), nbytes=nb,
-                tag=_shape_tag(f"B{B} {H}x{W} {Cin}->{Cout} s{ctx.stride}"))
-        dw = None
-        if ctx.needs_input_grad[1]:
-            sk = _sink(ctx.params[0])
-            if sk is not None:
-                # (every tensor the deferred launch READS is named: a segmented capture keeps them alive and keeps the early part
-                # of AdamW away from the parameters among them -- the folded BatchNorm's gamma / beta)
-                on_wgrad_stream(lambda: wgrad(sk), dy, x, *((mean, invstd, gamma, beta) if ctx.lazy else ()), sink=sk)
-            else:
-                dw = _emit(ctx.params[0], wgrad, True)
-        return dx, dw, None, None, None, None
-
-
-def _conv_pp(a, w_param, w_cl):
-    """operand pointers of a 3x3 product (activation or gradient `a`, weight parameter `w_param` whose kernel layout is `w_cl`)"""
-    pa, pw = h2_pp(a, w_param, w_b=True)
-    return pa, (pw if pw != P(w_param) else P(w_cl))
+            _conv_dgrad(dy, wp, w, dx, ctx.bn_link)
+        # (every tensor the deferred launch READS is named: a segmented capture keeps them alive and keeps the early part of AdamW away
+        # from the parameters among them -- the folded BatchNorm's gamma / beta)
+        dw = _wgrad(wp, lambda out: _conv_wgrad(dy, x, out, ctx.stride, bn, ctx.h2_in), ctx.needs_input_grad[1], dy, x, *bn)
+        return dx, dw, None
 
 
 def conv3x3_bnin_ok(xshape, Cout):
@@ -1726,10 +1786,7 @@ def conv3x3_bnin_ok(xshape, Cout):
 
 
 def conv3x3(x, w, stride=1, stats=False):
-    link = getattr(x, "_bn_link", None)
-    if link is not None and not (torch.is_grad_enabled() and x.requires_grad and cfg.bn_bwd_fuse):
-        link = None
-    return Conv3x3Fn.apply(x, w, stride, stats, getattr(x, "_bn_lazy", None), link)
+    return Conv3x3Fn.apply(x, w, _ConvOpts(stride, stats, getattr(x, "_bn_lazy", None), _bn_link_of(x)))
 
 
 # ----------------------------------------------------------------------------------------------- BatchNorm
