@@ -988,6 +988,27 @@ int tris_crf_update_f32(const float* U, const float* g, const float* b, float wg
  * conf = fg_pred; conf[fg_pred == 0] = 255; conf[bg_pred + fg_pred == 0] = 0; out uint8 [N] */
 int tris_crf_combine_u8(const float* Q, int N, unsigned char* out, void* stream);
 
+/* ---- CLIP attention pooling, inference (csrc/attnpool.hip; CLIP/clip/model.py:58-104 AttentionPool2d), DESIGN section 20 ------
+ * f32 memory streams, 16-byte accesses along C, no atomics, every sum in index order: a launch is bitwise repeatable. */
+/* The token matrix of AttentionPool2d.forward (CLIP/clip/model.py:70-83: reshape, permute, mean, cat, F.interpolate of the
+ * positional grid (:76, bilinear, align_corners=False, no antialiasing also when shrinking), cat, add) in one launch.
+ * c4 [B][h][w][C] channels-last, pos [S*S+1][C]; T [B][hw+1][C]: row 0 = the mean over the hw pixels (summed in pixel order, one
+ * division) + pos[0]; row 1+i = pixel i + the S x S grid pos[1:] resized to h x w.  Source positions are exact rationals and every
+ * weight one float division (csrc/bilinear.h lerp_exact_of); with h = w = S the pixel rows are c4 + pos[1:] bit for bit.
+ * B, h, w, S >= 1, hw + 1 <= TRIS_ATTNPOOL_LMAX, C % 4 == 0, B <= 65535, pointers 16-byte aligned, else hipErrorInvalidValue. */
+#define TRIS_ATTNPOOL_LMAX 1025
+int tris_attnpool_tokens_f32(const float* c4, const float* pos, float* T, int B, int h, int w, int C, int S, void* stream);
+/* One-query attention of every head against the tokens themselves (the folded form of CLIP/clip/model.py:84-102 for the global
+ * embedding): P[b][hd][j] = softmax_j(scale * T[b][j] . U[b][hd]) -- the maximum subtracted, the sum in key
+ * order, one division per element -- and pooled[b][hd] = sum_j P[b][hd][j] T[b][j], summed in key order.
+ * T [B][L][C]; U and pooled: element (b, hd, c) at b * strideB + hd * strideH + c (floats; both strides % 4 == 0), the same strides
+ * for both, so a head-major [heads][B][C] buffer (what a per-head batched product reads and writes) needs no transpose;
+ * P [B][heads][L] contiguous.  One workgroup per image and group of 8 heads (4, 2, 1: the largest that divides heads).
+ * B, heads >= 1, 1 <= L <= TRIS_ATTNPOOL_LMAX, C % 4 == 0, B * heads / group <= 2^31 - 1, pointers 16-byte aligned, else
+ * hipErrorInvalidValue. */
+int tris_attnpool_pool_f32(const float* T, const float* U, long strideB, long strideH, float scale, float* P, float* pooled, int B,
+                           int L, int C, int heads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,8 +6,8 @@ from `tris_amd.ops` (HIP kernels, channels-last activations).  Nothing here runs
 be constructed, moved and (de)serialised anywhere, `forward` needs the GPU.
 
   Bottleneck              CLIP/clip/model.py:10-55
-  AttentionPool2d         :58-104   (parameters kept for checkpoints; output is discarded by Stage-1)
-  ModifiedResNet          :195-279  (returns (c1,c2,c3,c4,[global,local]))
+  AttentionPool2d         :58-104   (inference only; Stage-1 discards its output and never runs it)
+  ModifiedResNet          :195-279  (returns (c1,c2,c3,c4,None); (c1,c2,c3,c4,[global,local]) with pool=True)
   ResidualAttentionBlock  :366-386,  Transformer :389-397,  VisionTransformer :400-448
   CLIP                    :451-580  (encode_text returns (all tokens, projected EOT token) :552-564)
   build_model             :607-644
@@ -163,8 +163,10 @@ class Linear(nn.Module):
 
 
 class AttentionPool2d(nn.Module):
-    """Kept for state-dict compatibility.  Stage-1 discards its output (model/model_stage1.py:59), so the
-    MI355X path never executes it; calling it raises."""
+    """CLIP's attention pooling (CLIP/clip/model.py:58-104), forward only, for inference.  Stage-1 and Stage-2
+    discard its output (model/model_stage1.py:59) and never call it; ModifiedResNet.forward(x, pool=True), ModifiedResNet.encode_pooled
+    and CLIP.forward do.  Its parameters never receive a gradient: there is no backward, and an input that requires grad while grad
+    mode is on raises NotImplementedError instead of being detached silently."""
 
     def __init__(self, spacial_dim, embed_dim, num_heads, output_dim=None):
         super().__init__()
@@ -177,8 +179,64 @@ class AttentionPool2d(nn.Module):
         for p in self.parameters():
             p._tris_no_grad_path = True  # never receives a gradient in Stage-1
 
-    def forward(self, x):
-        raise NotImplementedError("AttentionPool2d output is unused by TRIS Stage-1 and is not part of the MI355X path")
+        self._qkv_cat = None     # (key, [3C,C] weight, [3C] bias): see _qkv()
+
+    def _qkv(self):
+        """q/k/v weights and biases as ONE [3C, C] / [3C] operand, so the full form is one dense product over the tokens.  Built once
+        per module and rebuilt when any of the six tensors changes version or storage (an optimiser step, load_state_dict, .to():
+        the pattern of ops._PL_CONST)."""
+        six = (self.q_proj.weight, self.k_proj.weight, self.v_proj.weight, self.q_proj.bias, self.k_proj.bias, self.v_proj.bias)
+        key = tuple((t._version, t.data_ptr(), t.device) for t in six)
+        c = getattr(self, "_qkv_cat", None)
+        if c is None or c[0] != key:
+            with torch.no_grad():
+                c = self._qkv_cat = (key, torch.cat(six[:3], 0).contiguous(), torch.cat(six[3:], 0).contiguous())
+        return c[1], c[2]
+
+    def _channels_last(self, x):
+        """x is NCHW [B,C,h,w] as the reference passes it, or channels-last [B,h,w,C] as forward_cl returns it.  Told apart by where
+        embed_dim sits: shape[1] == embed_dim reads as NCHW (the reference's convention wins where both fit), otherwise shape[3] must
+        be embed_dim.  The NCHW-shaped views that ModifiedResNet.forward hands out are channels-last in memory and are not copied."""
+        if x.dim() != 4:
+            raise ValueError(f"AttentionPool2d: a 4-d feature map expected, got {tuple(x.shape)}")
+        if x.shape[1] == self.embed_dim:
+            return ops.nchw_to_nhwc(ops.unplanes(x))
+        if x.shape[3] != self.embed_dim:
+            raise ValueError(f"AttentionPool2d: neither [B,{self.embed_dim},h,w] nor [B,h,w,{self.embed_dim}]: {tuple(x.shape)}")
+        return ops.unplanes(x)
+
+    def forward(self, x, global_only=False):
+        """-> (global_feat [B,out], feature_map [B,out,h,w]) as CLIP/clip/model.py:101-104 (feature_map is an NCHW-shaped view of a
+        channels-last buffer, like every map this package hands out), or, global_only=True, global_feat alone through the folded
+        form, which never projects keys or values of the hw+1 tokens (no product has more than B * heads rows)."""
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("AttentionPool2d.forward is forward only (no backward kernel): call it under torch.no_grad()")
+        with torch.no_grad():
+            x = self._channels_last(x)
+            B, h, w, C = x.shape
+            T = ops.attnpool_tokens(x, self.positional_embedding, self.spacial_dim)       # [B, hw+1, C]
+            if global_only:
+                return self._global_folded(T)
+            if C != 64 * self.num_heads:
+                raise NotImplementedError(f"AttentionPool2d: the full form runs on ops.mha (head dim 64), got {C} / {self.num_heads}")
+            wqkv, bqkv = self._qkv()
+            o = self.c_proj(ops.mha(ops.linear(T, wqkv, bqkv), self.num_heads, False))      # [B, hw+1, out]
+            return ops.token0(o), o[:, 1:].unflatten(1, (h, w)).permute(0, 3, 1, 2)
+
+    def _global_folded(self, T):
+        """Token 0 of the full form without K and V of the other tokens.  Per head h (rows h d .. (h+1) d of the projections, d = C / heads),
+        with q_h = W_q,h t_0 + b_q,h: the logit of key j is (t_j . W_k,h^T q_h + q_h . b_k,h) / sqrt(d); the second term does not depend
+        on j and cancels in the softmax, so the scores need only u_h = W_k,h^T q_h.  The probabilities sum to 1, so the head's output
+        sum_j p_hj (W_v,h t_j + b_v,h) is W_v,h (sum_j p_hj t_j) + b_v,h."""
+        B, L, C = T.shape
+        H = self.num_heads
+        d = C // H
+        q0 = self.q_proj(ops.token0(T))                                                   # [B, C]
+        U = ops.bmm(q0.view(B, H, d).transpose(0, 1), self.k_proj.weight.view(H, d, C))    # [H, B, C]: u_h of every image
+        _, pooled = ops.attnpool_pool(T, U.transpose(0, 1), d ** -0.5)                     # [B, H, C], head-major in memory
+        o = ops.bmm(pooled.transpose(0, 1), self.v_proj.weight.view(H, d, C), tB=True)     # [H, B, d]
+        o = ops.axpy_bcast(o.transpose(0, 1).reshape(B, C), self.v_proj.bias, 1.0)
+        return self.c_proj(o)
 
 
 class ModifiedResNet(nn.Module):
@@ -244,11 +302,24 @@ class ModifiedResNet(nn.Module):
                 hooks[stage]()
         return tuple(outs)
 
-    def forward(self, x):
+    def forward(self, x, pool=False):
+        """pool=True: the fifth element is [x_global, x_local] as in the reference (CLIP/clip/model.py:276-277; inference only, computed
+        without gradient); by default it stays None -- every Stage-1 / Stage-2 caller discards it."""
         # reference returns NCHW tensors; hand out NCHW-shaped views of the channels-last buffers (no copy)
-        outs = [ops.unplanes(o).permute(0, 3, 1, 2) for o in self.forward_cl(x)]   # (h2 operand planes: callers get fp32 values)
-        outs.append(None)  # [x_global, x_local] of attnpool: discarded by every Stage-1 caller
+        cl = self.forward_cl(x)
+        outs = [ops.unplanes(o).permute(0, 3, 1, 2) for o in cl]   # (h2 operand planes: callers get fp32 values)
+        if pool:
+            x_global, x_local = self.attnpool(ops.unplanes(cl[-1]).detach())
+            outs.append([x_global, x_local])
+        else:
+            outs.append(None)  # [x_global, x_local] of attnpool: discarded by every Stage-1 caller
         return tuple(outs)
+
+    def encode_pooled(self, x):
+        """x [B,3,H,W] -> x_global [B, output_dim], the image embedding of CLIP's zero-shot path, through the folded form of the attention
+        pooling (AttentionPool2d._global_folded).  Inference only: runs without gradient."""
+        with torch.no_grad():
+            return self.attnpool(self.forward_cl(x)[-1], global_only=True)
 
 
 class LayerNorm(nn.Module):
@@ -523,8 +594,25 @@ class CLIP(nn.Module):
             x = self.ln_final(x)
         return ops.matmul(ops.eot_gather_packed(x, plan, N), self.text_projection)
 
+    def encode_image_pooled(self, image):
+        """image [B,3,H,W] -> the image embedding [B, embed_dim] of either visual tower: the ViT's forward returns it; the ModifiedResNet's
+        is x_global of its attention pooling (ModifiedResNet.encode_pooled).  Inference only: runs without gradient."""
+        with torch.no_grad():
+            if isinstance(self.visual, ModifiedResNet):
+                return self.visual.encode_pooled(image)
+            return self.visual(image)
+
     def forward(self, image, text):
-        raise NotImplementedError("CLIP.forward (zero-shot logits) is not on the Stage-1 path")
+        """Zero-shot logits (CLIP/clip/model.py:566-580): (logits_per_image [B,N], logits_per_text [N,B]) = logit_scale.exp() times the
+        cosine similarities of the l2-normalised image and text embeddings.  Inference only: runs without gradient.
+        PROJECT RULE: the reference's own forward works for the ViT tower only -- its ModifiedResNet returns a tuple, which :571 would
+        divide.  For the ModifiedResNet the image embedding is x_global of the attention pooling, which is what OpenAI's CLIP computes
+        (DESIGN.md section 20)."""
+        with torch.no_grad():
+            image_features = ops.l2norm(self.encode_image_pooled(image))
+            text_features = ops.l2norm(self.encode_text(text)[1])
+            logits_per_image = ops.matmul(image_features, text_features, tB=True) * self.logit_scale.exp()
+            return logits_per_image, logits_per_image.t()
 
 
 def convert_weights(model):

@@ -26,6 +26,25 @@ __device__ __forceinline__ Lerp lerp_of(int dst, int in, int out, int align) {
   l.w1 = src - (float)l.i0;
   return l;
 }
+// The align_corners=False position of lerp_of as the exact rational (in (2 dst + 1) - out) / (2 out), clamped at 0: the index by integer
+// division, each weight by ONE float division of its own numerator (w0 is not 1 - w1), so both carry a RELATIVE error of 2^-24 however
+// small they are.  lerp_of's float position is off by a few ulps of the POSITION, an absolute error in the weight that an element-wise
+// bound in terms of sum_k w_k |v_k| cannot absorb (csrc/attnpool.hip: the positional grid of AttentionPool2d).  Same indices as lerp_of
+// wherever the float position does not round across an integer.  in, out <= 2^14.
+struct LerpQ { int i0, i1; float w0, w1; };
+__device__ __forceinline__ LerpQ lerp_exact_of(int dst, int in, int out) {
+  int num = in * (2 * dst + 1) - out;
+  const int den = 2 * out;
+  if (num < 0) num = 0;
+  LerpQ l;
+  l.i0 = num / den;
+  const int r = num - l.i0 * den;
+  if (l.i0 > in - 1) l.i0 = in - 1;
+  l.i1 = l.i0 + (l.i0 < in - 1 ? 1 : 0);
+  l.w1 = (float)r / (float)den;
+  l.w0 = (float)(den - r) / (float)den;
+  return l;
+}
 // weight with which input index `y` contributes to output index `dst`
 __device__ __forceinline__ float contrib(int dst, int in, int out, int align, int y) {
   Lerp l = lerp_of(dst, in, out, align);

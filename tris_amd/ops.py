@@ -2522,6 +2522,70 @@ def token0(x):
     return EotGatherFn.apply(None, x)
 
 
+# ----------------------------------------------------------------------------------------------- CLIP attention pooling (inference)
+ATTNPOOL_LMAX = CONSTS["TRIS_ATTNPOOL_LMAX"]
+
+
+def _no_backward(name, *ts):
+    """the attention pooling has no backward (nothing trains through it in the reference's scripts): refuse to drop a gradient silently"""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise NotImplementedError(f"ops.{name} is forward only (no backward kernel): call it under torch.no_grad() or detach its inputs")
+
+
+def attnpool_tokens(c4_cl, pos, S):
+    """The token matrix of AttentionPool2d (CLIP/clip/model.py:70-83) in one launch: c4_cl [B,h,w,C] channels-last (fp32 or operand
+    planes), pos [S*S+1, C] -> T [B, hw+1, C]; row 0 = mean over the pixels + pos[0], row 1+i = pixel i + the S x S grid of pos[1:]
+    resized bilinearly to h x w (F.interpolate's defaults).  Forward only."""
+    _no_backward("attnpool_tokens", c4_cl, pos)
+    if c4_cl.dim() != 4 or pos.dim() != 2:
+        raise ValueError(f"ops.attnpool_tokens: c4_cl [B,h,w,C] and pos [S*S+1,C] expected, got {tuple(c4_cl.shape)} and {tuple(pos.shape)}")
+    B, h, w, C = c4_cl.shape
+    if C % 4 or C < 4:
+        raise ValueError(f"ops.attnpool_tokens: C % 4 == 0 required, got C = {C}")
+    if h * w + 1 > ATTNPOOL_LMAX:
+        raise ValueError(f"ops.attnpool_tokens: L = h*w + 1 = {h * w + 1} exceeds the limit L <= {ATTNPOOL_LMAX}")
+    if S < 1 or tuple(pos.shape) != (S * S + 1, C):
+        raise ValueError(f"ops.attnpool_tokens: pos must be [S*S+1, C] = [{S * S + 1}, {C}], got {tuple(pos.shape)}")
+    if B < 1 or B > 65535 or h < 1 or w < 1:
+        raise ValueError(f"ops.attnpool_tokens: 1 <= B <= 65535 and a non-empty map required, got {tuple(c4_cl.shape)}")
+    _chk(c4_cl, pos)
+    with torch.no_grad():
+        x = unplanes(c4_cl).contiguous()
+        pos = pos.detach().contiguous()
+        T = torch.empty(B, h * w + 1, C, device=x.device, dtype=torch.float32)
+        call("tris_attnpool_tokens_f32", P(x), P(pos), P(T), B, h, w, C, S, _stream())
+    return T
+
+
+def attnpool_pool(T, U, scale):
+    """The one-query attention of the folded global embedding: T [B,L,C] tokens, U [B,heads,C] (contiguous, or the
+    transposed view of a dense head-major [heads,B,C] buffer -- what a per-head ops.bmm writes and reads: taken as it is, no copy) ->
+    (P [B,heads,L] = softmax_j(scale * T[b,j] . U[b,h]), pooled [B,heads,C] = sum_j P[b,h,j] T[b,j], laid out in memory like U).
+    Forward only."""
+    _no_backward("attnpool_pool", T, U)
+    if T.dim() != 3 or U.dim() != 3 or U.shape[0] != T.shape[0] or U.shape[2] != T.shape[2]:
+        raise ValueError(f"ops.attnpool_pool: T [B,L,C] and U [B,heads,C] expected, got {tuple(T.shape)} and {tuple(U.shape)}")
+    B, L, C = T.shape
+    heads = U.shape[1]
+    if C % 4 or C < 4:
+        raise ValueError(f"ops.attnpool_pool: C % 4 == 0 required, got C = {C}")
+    if L < 1 or L > ATTNPOOL_LMAX:
+        raise ValueError(f"ops.attnpool_pool: L = {L} outside the limit 1 <= L <= {ATTNPOOL_LMAX}")
+    if B < 1 or heads < 1:
+        raise ValueError(f"ops.attnpool_pool: B >= 1 and heads >= 1 required, got {tuple(U.shape)}")
+    _chk(T, U)
+    with torch.no_grad():
+        T = unplanes(T).contiguous()
+        U = unplanes(U).detach()
+        head_major = U.stride() == (C, B * C, 1)          # the [B,heads,C] view of a dense [heads,B,C] buffer
+        if not head_major:
+            U = U.contiguous()
+        Pr = torch.empty(B, heads, L, device=T.device, dtype=torch.float32)
+        pooled = torch.empty_strided((B, heads, C), U.stride(), device=T.device, dtype=torch.float32)
+        call("tris_attnpool_pool_f32", P(T), P(U), U.stride(0), U.stride(1), float(scale), P(Pr), P(pooled), B, L, C, heads, _stream())
+    return Pr, pooled
+
+
 # ----------------------------------------------------------------------------------------------- heads
 class L2NormFn(torch.autograd.Function):
     @staticmethod
