@@ -1009,6 +1009,36 @@ int tris_attnpool_tokens_f32(const float* c4, const float* pos, float* T, int B,
 int tris_attnpool_pool_f32(const float* T, const float* U, long strideB, long strideH, float scale, float* P, float* pooled, int B,
                            int L, int C, int heads, void* stream);
 
+/* ---- Scoring response maps, CRF labels and pseudo masks against REFER ground truth (csrc/labelscore.hip; the passes
+ * IRNet/run_sample_refer.py:59,98,102 names and the reference does not ship), DESIGN section 21 -----------------------------------
+ * The ground truth stays the (ends, seg_off) arena of tris_rle_decode_sum_u8; no full-size target is formed.  The count c of pixel
+ * (y, x) is the number of segments seg_lo .. seg_hi - 1 whose run holding position x*H + y has an odd index (a position past the last
+ * run counts 0).  Its bit: gt_rule 0 -> c == 1 (dataset/ReferDataset.py load_mask: annot[ref_mask == 1] = 1), gt_rule 1 -> c != 0
+ * (validate.py:183-190 on target != 0, ReferIt).  Every workgroup counts in LDS and stores one int32 partial row; a second launch sums
+ * the rows in block order into int64: no global atomics, the same bytes on every run.  A ref's runs are staged in LDS when all of them
+ * fit tris_score_stage_capacity() words and searched in global memory otherwise.  workspace: tris_score_workspace_bytes(G, H, W,
+ * bins) bytes, bins = T + 1 for the maps and 256 (G = 1) for the counts; -1 for arguments out of range.
+ * The host checks what the device cannot refuse: ranges inside the arena and at most 255 segments long, thresholds finite and
+ * strictly ascending. */
+int tris_score_stage_capacity(void);
+long tris_score_workspace_bytes(int G, int H, int W, int bins);
+/* validate.py:183-190 and utils/util.py compute_mask_IU (pred = map.gt(thr); I = sum(pred & target), U = sum(pred | target)) for G
+ * maps of one size and a whole threshold list in one pass: maps float32 [G][H][W] row-major, ranges int32 [G][2] the ref of each map,
+ * thresholds float32 [T] strictly ascending and finite, 1 <= T <= 64.  hist int64 [G][T + 1][2]: hist[g][b][bit] = the pixels of map g
+ * with exactly b thresholds strictly below their value (float32 comparison: a value equal to a threshold is not above it, a NaN is
+ * above none, +inf above all) and that ground-truth bit.  For threshold j: I = sum_{b > j} hist[b][1],
+ * U = sum_{b > j} hist[b][0] + sum_b hist[b][1].  G <= 65535, H*W <= 2^24, else hipErrorInvalidValue. */
+int tris_score_maps_f32(const float* maps, const int* ends, const long* seg_off, const int* ranges, int G, int H, int W,
+                        const float* thresholds, int T, int gt_rule, long* hist, void* workspace, void* stream);
+/* A uint8 stack [K][H][W] against one ref: hist int64 [256][2], hist[s][bit] = the pixels whose byte sum over the K planes (mod 256;
+ * a bool stack of K <= 255 cannot wrap) is s and that carry that ground-truth bit.  K = 1: a label image of
+ * IRNet/step_refer/cam_to_ir_label.py:72-76 (1 object, 0 background, 255 neither).  A bool stack: the instance masks of
+ * IRNet/step_refer/make_ins_seg_labels.py:160-163, whose sum dataset/ReferDataset.py's pseudo loading turns into the Stage-2 target
+ * (s > 0 predicted, s > 1 overlapping).  K = 0: nothing is read (stack may be NULL), every pixel has sum 0.  0 <= K <= 255,
+ * seg_hi - seg_lo <= 255, H*W <= 2^24, else hipErrorInvalidValue. */
+int tris_score_counts_u8(const unsigned char* stack, int K, const int* ends, const long* seg_off, int seg_lo, int seg_hi, int H, int W,
+                         int gt_rule, long* hist, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

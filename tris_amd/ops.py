@@ -3717,6 +3717,148 @@ def rle_target_nearest(arena, lo, hi, H, W, S, out=None):
     return out
 
 
+# ------------------------------------------------------ scoring artefacts against REFER ground truth (csrc/labelscore.hip)
+SCORE_MAX_THRESHOLDS = 64
+
+
+def _score_arena(arena, who):
+    """(ends, seg_off) of an arena argument, contiguous, on the device, of the arena's dtypes"""
+    ends, seg_off = (arena.ends, arena.seg_off) if hasattr(arena, "ends") else arena
+    for t, dt, name in ((ends, torch.int32, "ends"), (seg_off, torch.int64, "seg_off")):
+        if not t.is_cuda:
+            raise NoGpuError(f"tris_amd ops run on MI355X only ({who}: {name} is a CPU tensor); there is no CPU fallback")
+        if t.dtype != dt:
+            raise TypeError(f"{who}: {name} is {t.dtype}, expected {dt}")
+    if seg_off.numel() < 1:
+        raise ValueError(f"{who}: seg_off is empty (an arena of n segments has n + 1 offsets)")
+    return ends.contiguous(), seg_off.contiguous()
+
+
+def _score_canvas(H, W, who):
+    if H < 1 or W < 1 or H * W > (1 << 24):
+        raise ValueError(f"{who}: H*W = {H}x{W} is empty or beyond 2^24 pixels")
+
+
+def _score_rule(gt_rule, who):
+    if gt_rule not in (0, 1):
+        raise ValueError(f"{who}: gt_rule {gt_rule!r} is neither 0 (covered exactly once) nor 1 (covered at all)")
+
+
+def _score_range(lo, hi, n_seg, who):
+    if not 0 <= lo <= hi <= n_seg:
+        raise ValueError(f"{who}: segments {lo}..{hi} lie outside the arena's {n_seg}")
+    if hi - lo > 255:
+        raise ValueError(f"{who}: segments {lo}..{hi} are {hi - lo}, more than the 255 a ref may have")
+
+
+class ScoreThresholds:
+    """a threshold list checked once: finite, strictly ascending as float32, 1 .. 64 entries.  `.given` the values as they came, `.host` float32
+    numpy (what is compared), `.dev(device)` the device copy (made once per device), so that a sweep over many groups neither re-checks nor re-uploads it."""
+
+    def __init__(self, values):
+        import numpy as np
+        if torch.is_tensor(values):
+            values = values.detach().cpu().numpy()
+        v = np.asarray(values, np.float64).reshape(-1)
+        if not 1 <= v.size <= SCORE_MAX_THRESHOLDS:
+            raise ValueError(f"thresholds: T = {v.size} entries, expected 1 .. {SCORE_MAX_THRESHOLDS}")
+        with np.errstate(over="ignore"):
+            f = v.astype(np.float32)
+        bad = np.nonzero(~np.isfinite(f))[0]
+        if bad.size:
+            raise ValueError(f"thresholds: entry {int(bad[0])} = {float(v[bad[0]])} is not finite")
+        bad = np.nonzero(~(f[1:] > f[:-1]))[0]
+        if bad.size:
+            j = int(bad[0])
+            raise ValueError(f"thresholds: not strictly ascending in float32: entry {j} = {float(f[j])!r}, entry {j + 1} = "
+                             f"{float(f[j + 1])!r}")
+        self.given, self.host, self._dev = [float(x) for x in v], f, {}
+
+    def __len__(self):
+        return self.host.size
+
+    def dev(self, device):
+        t = self._dev.get(device)
+        if t is None:
+            t = self._dev[device] = torch.from_numpy(self.host.copy()).to(device)
+        return t
+
+
+def score_maps(maps, arena, ranges, thresholds, gt_rule=0):
+    """validate.py:183-190 for G maps of one size and a whole threshold sweep in one pass, against refs that stay run ends: maps
+    float32 [G,H,W]; arena = (ends, seg_off) on the device or an object with those attributes; ranges [G,2] = the segments lo .. hi-1 of
+    each map's ref (a host sequence / numpy array, or an int32 device tensor, which is read back to be checked); thresholds a host
+    sequence or a ScoreThresholds -> int64 [G, T+1, 2] on the device: [g, b, bit] = the pixels of map g with exactly b thresholds
+    strictly below their value (float32) and that ground-truth bit (gt_rule 0: covered by exactly one segment, ReferDataset.load_mask;
+    1: covered at all, validate's target != 0).  Two launches whatever G and T are; no host synchronisation with host ranges."""
+    import numpy as np
+    who = "score_maps"
+    if not torch.is_tensor(maps) or not maps.is_cuda:
+        raise NoGpuError("tris_amd ops run on MI355X only (score_maps: maps is not a device tensor); there is no CPU fallback")
+    if maps.dtype != torch.float32:
+        raise TypeError(f"{who}: maps is {maps.dtype}, expected torch.float32")
+    if maps.dim() != 3:
+        raise ValueError(f"{who}: maps is [G,H,W], got {tuple(maps.shape)}")
+    ends, seg_off = _score_arena(arena, who)
+    G, H, W = maps.shape
+    _score_canvas(H, W, who)
+    _score_rule(gt_rule, who)
+    if G > 65535:
+        raise ValueError(f"{who}: G = {G} maps in one call, at most 65535")
+    thr = thresholds if isinstance(thresholds, ScoreThresholds) else ScoreThresholds(thresholds)
+    if torch.is_tensor(ranges):
+        if not ranges.is_cuda:
+            raise NoGpuError("tris_amd ops run on MI355X only (score_maps: ranges is a CPU tensor); there is no CPU fallback")
+        if ranges.dtype != torch.int32:
+            raise TypeError(f"{who}: ranges is {ranges.dtype}, expected torch.int32")
+        host_ranges, dev_ranges = ranges.cpu().numpy(), ranges.contiguous()
+    else:
+        host_ranges, dev_ranges = np.asarray(ranges, np.int64), None
+    if host_ranges.shape != (G, 2):
+        raise ValueError(f"{who}: ranges is [G,2] = [{G},2], got {tuple(host_ranges.shape)}")
+    n_seg = seg_off.numel() - 1
+    for g, (lo, hi) in enumerate(host_ranges.tolist()):
+        _score_range(lo, hi, n_seg, f"{who}: map {g}")
+    if dev_ranges is None:
+        dev_ranges = torch.from_numpy(host_ranges.astype(np.int32)).to(maps.device)
+    T = len(thr)
+    hist = torch.empty(G, T + 1, 2, dtype=torch.int64, device=maps.device)
+    if G:
+        ws = workspace(query("tris_score_workspace_bytes", G, H, W, T + 1))
+        call("tris_score_maps_f32", P(maps.contiguous()), P(ends), P(seg_off), P(dev_ranges), G, H, W, P(thr.dev(maps.device)), T,
+             gt_rule, P(hist), P(ws), _stream())
+    return hist
+
+
+def score_counts(stack_u8, arena, lo, hi, H, W, gt_rule=0):
+    """a uint8 stack [K,H,W] (or an [H,W] image: K = 1; K = 0 allowed) against the ref of segments lo .. hi-1 -> int64 [256,2] on the
+    device: [s, bit] = the pixels whose byte sum over the K planes is s (mod 256) and that carry that ground-truth bit.  A label image
+    of cam_to_ir_label fills rows 1 / 0 / 255; a bool stack viewed as bytes scores instance masks (s > 0 predicted, s > 1 overlapping,
+    the pixels Stage 2 gives a target of 2).  Two launches, no host synchronisation."""
+    who = "score_counts"
+    if not torch.is_tensor(stack_u8) or not stack_u8.is_cuda:
+        raise NoGpuError("tris_amd ops run on MI355X only (score_counts: the stack is not a device tensor); there is no CPU fallback")
+    if stack_u8.dtype != torch.uint8:
+        raise TypeError(f"{who}: the stack is {stack_u8.dtype}, expected torch.uint8 (view a bool stack as bytes)")
+    ends, seg_off = _score_arena(arena, who)
+    H, W = int(H), int(W)
+    _score_canvas(H, W, who)
+    _score_rule(gt_rule, who)
+    if stack_u8.dim() == 2:
+        stack_u8 = stack_u8.unsqueeze(0)
+    if stack_u8.dim() != 3 or tuple(stack_u8.shape[1:]) != (H, W):
+        raise ValueError(f"{who}: the stack is [K,{H},{W}], got {tuple(stack_u8.shape)}")
+    K = stack_u8.shape[0]
+    if K > 255:
+        raise ValueError(f"{who}: K = {K} planes, their sum does not fit a byte (at most 255)")
+    _score_range(int(lo), int(hi), seg_off.numel() - 1, who)
+    hist = torch.empty(256, 2, dtype=torch.int64, device=ends.device)
+    ws = workspace(query("tris_score_workspace_bytes", 1, H, W, 256))
+    call("tris_score_counts_u8", P(stack_u8.contiguous()) if K else None, K, P(ends), P(seg_off), int(lo), int(hi), H, W, gt_rule,
+         P(hist), P(ws), _stream())
+    return hist
+
+
 def eval_post_group(maps, targets_u8, signed=False, cams=True):
     """validate_referit.py:160-171 for the K sentences of one image in one call: maps [K,S,S] (or [K,1,S,S]), targets_u8 [K,oH,oW]
     counts -> (records int64 [K,4] on the device = I, U, first arg-max of cam, target count at the arg-max; cams [K,oH,oW], None
