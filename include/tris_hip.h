@@ -1038,6 +1038,21 @@ int tris_score_maps_f32(const float* maps, const int* ends, const long* seg_off,
  * seg_hi - seg_lo <= 255, H*W <= 2^24, else hipErrorInvalidValue. */
 int tris_score_counts_u8(const unsigned char* stack, int K, const int* ends, const long* seg_off, int seg_lo, int seg_hi, int H, int W,
                          int gt_rule, long* hist, void* workspace, void* stream);
+/* The same stack against the same ref, plane by plane and optionally at the Stage-2 training resolution (the instance pass
+ * IRNet/run_sample_refer.py:102 --eval_ins_seg_pass names; IRNet/step_refer/make_ins_seg_labels.py:95-101 keeps the fragments it
+ * scores 0 in 'mask', and dataset/ReferDataset.py sums all planes).  table int64 [K + 3][2], second index the ground-truth bit of the
+ * sample; with s = sum_k stack[k] as an integer (no byte wrap): row 0 s == 0, row 1 s == 1, row 2 s >= 2, row 3 + k stack[k] != 0.
+ * yidx int32 [Hout], xidx int32 [Wout] are the index tables of tris_gather2d_u8: the samples are the multiset (yidx[y], xidx[x]), a
+ * repeated index counts as often as it appears, an entry < 0 (or beyond the canvas) is a sample with every plane 0 and bit 0, as
+ * tris_mask_sum_nearest_u8 and tris_rle_target_nearest_u8 write 0 there: rows 0 .. 2 are the histogram of the one against the other.
+ * Both NULL: every pixel once, Hout == H and Wout == W.  The host guarantees that the entries >= 0 of a table do not decrease (Pillow's
+ * NEAREST tables do not): the run walk goes forward only, and a table that went back would give wrong bits (no read outside the
+ * runs).  Tiles are of the output grid; workspace: tris_score_planes_workspace_bytes(K, Hout, Wout) bytes (K + 3 may exceed the 256
+ * bins of tris_score_workspace_bytes), -1 for arguments out of range.  0 <= K <= 255 (K = 0: stack may be NULL), seg_hi - seg_lo <=
+ * 255, H*W <= 2^24, Hout*Wout <= 2^24, one table NULL and the other not, else hipErrorInvalidValue. */
+long tris_score_planes_workspace_bytes(int K, int Hout, int Wout);
+int tris_score_planes_u8(const unsigned char* stack, int K, const int* ends, const long* seg_off, int seg_lo, int seg_hi, int H, int W,
+                         const int* yidx, const int* xidx, int Hout, int Wout, int gt_rule, long* table, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,12 @@ each (a 14-vertex blob, a few hundred runs).  Four routes to the same I and U of
 * host       -- cocomask.frPyObjects + decode of every ref and numpy comparisons per threshold (one pass, wall clock).
 Every route is compared with the host route before it is timed.
 
+A fifth route, score_planes (ops.score_planes), has a shape of its own: K = 4 instance masks of 480 x 640 against one of the refs.
+It is timed beside the composition that gave the same [K+3, 2] table before the op existed -- K + 1 calls of ops.score_counts, the
+stack and each plane alone -- with the two alternated window by window in one process (windows of 100 x `inner` calls), and alone on the 320 x 320 NEAREST grid
+(which the composition cannot score).  Both are compared with a numpy count over the host-rasterised ref first.  Its line carries the
+median and the lowest and highest window of each.
+
 A timed window is `inner` back-to-back calls between two HIP events on the current stream, after a warm-up; the median of `reps`
 windows divided by `inner` and by the 8 names is reported.  Every route runs in a child process of its own under a time limit of
 `limit` seconds, and nothing more is started after one that fails.  One JSON line per route.
@@ -27,7 +33,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 G, H, W = 8, 480, 640
-ROUTES = ("score_maps", "launches", "device", "host")
+ROUTES = ("score_maps", "launches", "device", "host", "score_planes")
+K_PLANES, TRAIN_SIZE = 4, 320
 
 
 def scene():
@@ -81,10 +88,88 @@ def host_iu(maps, polys, thr):
     return I, U
 
 
+def planes_scene(polys):
+    """-> (stack uint8 [K,H,W]: discs around the first ref's polygon and one fragment, ground truth bool [H,W] of that ref)"""
+    import numpy as np
+    from tris_amd.dataset import cocomask
+    gt = cocomask.decode(cocomask.frPyObjects([polys[0]], H, W)).sum(2) == 1
+    xy = np.asarray(polys[0]).reshape(-1, 2)
+    cx, cy = xy.mean(0)
+    ys, xs = np.mgrid[0:H, 0:W]
+    stack = np.zeros((K_PLANES, H, W), np.uint8)
+    for k, (dx, dy, r) in enumerate([(0, 0, 95), (40, -30, 70), (-120, 60, 50), (200, 150, 6)][:K_PLANES]):
+        stack[k] = (xs - cx - dx) ** 2 + (ys - cy - dy) ** 2 < r * r
+    return stack, gt
+
+
+def host_table(stack, gt, yi=None, xi=None):
+    """the [K+3, 2] table by numpy counting, on the samples (yi[y], xi[x]) when given (Pillow's NEAREST tables have no hole here)"""
+    import numpy as np
+    if yi is not None:
+        stack, gt = stack[:, yi[:, None], xi[None, :]], gt[yi[:, None], xi[None, :]]
+    s = stack.astype(np.int64).sum(0)
+    sels = [s == 0, s == 1, s >= 2] + [p != 0 for p in stack]
+    return np.array([[np.count_nonzero(sel & ~gt), np.count_nonzero(sel & gt)] for sel in sels], np.int64)
+
+
+def planes_route(reps, inner):
+    import numpy as np
+    import torch
+    from tris_amd import ops
+    from tris_amd.dataset import pil_tables
+    from tris_amd.dataset.poly_arena import PolyArena
+    _, polys, _ = scene()
+    stack, gt = planes_scene(polys)
+    arena = PolyArena()
+    lo, hi = arena.add_ref([polys[0]], H, W, "ref 0")
+    built = arena.build("cuda")
+    dev = torch.from_numpy(stack).cuda()
+    planes = [dev[k:k + 1].contiguous() for k in range(K_PLANES)]
+
+    def new():
+        return ops.score_planes(dev, built, lo, hi, H, W)
+
+    def new_train():
+        return ops.score_planes(dev, built, lo, hi, H, W, out_hw=TRAIN_SIZE)
+
+    def composed():
+        hist = ops.score_counts(dev, built, lo, hi, H, W)
+        rows = [hist[0], hist[1], hist[2:].sum(0)]
+        for p in planes:
+            rows.append(ops.score_counts(p, built, lo, hi, H, W)[1:].sum(0))
+        return torch.stack(rows)
+
+    want = host_table(stack, gt)
+    yi, xi = pil_tables.nearest_index(H, TRAIN_SIZE), pil_tables.nearest_index(W, TRAIN_SIZE)
+    assert yi.min() >= 0 and xi.min() >= 0
+    assert np.array_equal(new().cpu().numpy(), want), "score_planes disagrees with the host count"
+    assert np.array_equal(composed().cpu().numpy(), want), "the score_counts composition disagrees with the host count"
+    assert np.array_equal(new_train().cpu().numpy(), host_table(stack, gt, yi, xi)), "score_planes at 320 disagrees with the host count"
+    for fn in (new, composed, new_train):
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    inner *= 100                                                    # a call is some 10 us: windows of thousands of calls, not of 20
+    w = {"planes": [], "composed": [], "planes_320": []}
+    for _ in range(reps):                                           # alternated: one window of each, reps times
+        w["planes"].append(window(new, inner))
+        w["composed"].append(window(composed, inner))
+        w["planes_320"].append(window(new_train, inner))
+    row = {"route": "score_planes", "K": K_PLANES, "H": H, "W": W, "runs": int(built.seg_off[hi] - built.seg_off[lo]),
+           "clock": "device events, routes alternated window by window in one process"}
+    for key, v in w.items():
+        row[f"{key}_us_per_name"] = round(float(np.median(v)), 3)
+        row[f"{key}_us_low_high"] = [round(float(min(v)), 3), round(float(max(v)), 3)]
+    row.update(train_size=TRAIN_SIZE, device=torch.cuda.get_device_name(0), reps=reps, inner=inner)
+    print(json.dumps(row), flush=True)
+
+
 def route(name, reps, inner):
     import numpy as np
     import torch
     assert torch.cuda.is_available(), "pseudo_eval_bench needs the MI355X"
+    if name == "score_planes":
+        return planes_route(reps, inner)
     from tris_amd import ops, pseudo_eval as pe
     from tris_amd.dataset.poly_arena import PolyArena
     maps, polys, thr = scene()

@@ -3859,6 +3859,96 @@ def score_counts(stack_u8, arena, lo, hi, H, W, gt_rule=0):
     return hist
 
 
+def _score_table(values, n_in, who, axis):
+    """one index table of score_planes as int32 numpy: entries < 0 are samples of nothing, the others lie inside 0 .. n_in - 1 and do
+    not decrease (the kernel's run walk only goes forward); anything else is a ValueError naming the entry"""
+    import numpy as np
+    v = np.asarray(values)
+    if v.ndim != 1 or v.size < 1 or v.dtype.kind not in "iu":
+        raise ValueError(f"{who}: {axis} is a 1-D integer table of at least one entry, got {v.dtype} {tuple(v.shape)}")
+    v = v.astype(np.int64)
+    bad = np.nonzero(v >= n_in)[0]
+    if bad.size:
+        raise ValueError(f"{who}: {axis}[{int(bad[0])}] = {int(v[bad[0]])} lies outside the canvas's 0..{n_in - 1}")
+    at = np.nonzero(v >= 0)[0]
+    back = np.nonzero(np.diff(v[at]) < 0)[0]
+    if back.size:
+        j = int(at[back[0] + 1])
+        raise ValueError(f"{who}: {axis}[{j}] = {int(v[j])} is below an earlier entry {int(v[at[back[0]]])}: the table decreases")
+    return np.maximum(v, -1).astype(np.int32)
+
+
+def _score_out_hw(out_hw, who):
+    hw = (out_hw, out_hw) if isinstance(out_hw, int) and not isinstance(out_hw, bool) else out_hw
+    if (not isinstance(hw, (tuple, list)) or len(hw) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in hw)
+            or hw[0] < 1 or hw[1] < 1 or hw[0] * hw[1] > (1 << 24)):
+        raise ValueError(f"{who}: out_hw {out_hw!r} is neither None, a size S >= 1 nor (Hout, Wout) of at most 2^24 samples")
+    return int(hw[0]), int(hw[1])
+
+
+_SCORE_TABLES_OK = set()
+
+
+def _score_planes_args(stack_u8, arena, lo, hi, H, W, gt_rule, who):
+    if not torch.is_tensor(stack_u8) or not stack_u8.is_cuda:
+        raise NoGpuError(f"tris_amd ops run on MI355X only ({who}: the stack is not a device tensor); there is no CPU fallback")
+    if stack_u8.dtype != torch.uint8:
+        raise TypeError(f"{who}: the stack is {stack_u8.dtype}, expected torch.uint8 (view a bool stack as bytes)")
+    ends, seg_off = _score_arena(arena, who)
+    H, W = int(H), int(W)
+    _score_canvas(H, W, who)
+    _score_rule(gt_rule, who)
+    if stack_u8.dim() != 3 or tuple(stack_u8.shape[1:]) != (H, W):
+        raise ValueError(f"{who}: the stack is [K,{H},{W}], got {tuple(stack_u8.shape)}")
+    K = stack_u8.shape[0]
+    if K > 255:
+        raise ValueError(f"{who}: K = {K} planes, their sum does not fit a byte (at most 255)")
+    _score_range(int(lo), int(hi), seg_off.numel() - 1, who)
+    return stack_u8.contiguous(), ends, seg_off, K, H, W
+
+
+def _score_planes_launch(stack_u8, K, ends, seg_off, lo, hi, H, W, yi, xi, out_h, out_w, gt_rule):
+    table = torch.empty(K + 3, 2, dtype=torch.int64, device=ends.device)
+    ws = workspace(query("tris_score_planes_workspace_bytes", K, out_h, out_w))
+    call("tris_score_planes_u8", P(stack_u8) if K else None, K, P(ends), P(seg_off), int(lo), int(hi), H, W,
+         None if yi is None else P(yi), None if xi is None else P(xi), out_h, out_w, gt_rule, P(table), P(ws), _stream())
+    return table
+
+
+def score_planes(stack_u8, arena, lo, hi, H, W, out_hw=None, gt_rule=0):
+    """a uint8 stack [K,H,W] (0 <= K <= 255) against the ref of segments lo .. hi-1, plane by plane -> int64 [K+3, 2] on the device,
+    second index the ground-truth bit: rows 0 / 1 / 2 = the samples whose integer sum over the planes (no byte wrap) is 0 / 1 / at
+    least 2, row 3+k = the samples where plane k is not 0.  out_hw=None: every pixel once.  out_hw=(Hout, Wout) or a size S: the
+    source pixels Pillow's NEAREST resize to that size reads (the tables of mask_sum_nearest_u8 and rle_target_nearest), so rows
+    0 .. 2 are the histogram of Stage 2's resized pseudo target against its resized target.  Two launches, no host synchronisation."""
+    who = "score_planes"
+    stack_u8, ends, seg_off, K, H, W = _score_planes_args(stack_u8, arena, lo, hi, H, W, gt_rule, who)
+    if out_hw is None:
+        return _score_planes_launch(stack_u8, K, ends, seg_off, lo, hi, H, W, None, None, H, W, gt_rule)
+    out_h, out_w = _score_out_hw(out_hw, who)
+    for n_in, n_out, axis in ((H, out_h, "yidx"), (W, out_w, "xidx")):
+        if (n_in, n_out) not in _SCORE_TABLES_OK:                  # (Pillow's tables pass; checked once per size pair all the same)
+            from .dataset import pil_tables
+            _score_table(pil_tables.nearest_index(n_in, n_out), n_in, f"{who}: NEAREST {n_in} -> {n_out}", axis)
+            _SCORE_TABLES_OK.add((n_in, n_out))
+    yi, = _pil_tables("nearest", H, out_h, ends.device)
+    xi, = _pil_tables("nearest", W, out_w, ends.device)
+    return _score_planes_launch(stack_u8, K, ends, seg_off, lo, hi, H, W, yi, xi, out_h, out_w, gt_rule)
+
+
+def score_planes_at(stack_u8, arena, lo, hi, H, W, yidx, xidx, gt_rule=0):
+    """score_planes on the samples {(yidx[y], xidx[x])} of two host index tables (integer sequences): a repeated index counts as often
+    as it appears, an entry < 0 is a sample with every plane 0 and ground-truth bit 0.  The entries >= 0 of a table lie inside the
+    canvas and do not decrease, else a ValueError naming the entry.  The tables are uploaded on every call."""
+    who = "score_planes_at"
+    stack_u8, ends, seg_off, K, H, W = _score_planes_args(stack_u8, arena, lo, hi, H, W, gt_rule, who)
+    yi, xi = _score_table(yidx, H, who, "yidx"), _score_table(xidx, W, who, "xidx")
+    if yi.size * xi.size > (1 << 24):
+        raise ValueError(f"{who}: {yi.size}x{xi.size} samples are beyond 2^24")
+    return _score_planes_launch(stack_u8, K, ends, seg_off, lo, hi, H, W, torch.from_numpy(yi).to(ends.device),
+                                torch.from_numpy(xi).to(ends.device), int(yi.size), int(xi.size), gt_rule)
+
+
 def eval_post_group(maps, targets_u8, signed=False, cams=True):
     """validate_referit.py:160-171 for the K sentences of one image in one call: maps [K,S,S] (or [K,1,S,S]), targets_u8 [K,oH,oW]
     counts -> (records int64 [K,4] on the device = I, U, first arg-max of cam, target count at the arg-max; cams [K,oH,oW], None

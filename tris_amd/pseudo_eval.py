@@ -16,6 +16,9 @@ Three artefacts, three on-disk formats:
   score_cams    D/{name}.npy  float32 [H,W]                     -> int64 [N, T+1, 2]   per name: bin of the value x ground-truth bit
   score_labels  L/{name}.png  8-bit grey, 1 / 0 / 255           -> int64 [N, 3, 2]     rows: label 0, label 1, label 255
   score_masks   O/{name}.npy  dict with 'mask' bool [K,h,w]     -> int64 [N, 3, 2], K  rows: sum 0, sum 1, sum > 1
+  score_instances  the same file with its 'score' [K]           -> per name int64 [K+3, 2]   rows: sum 0, 1, > 1, then one per
+                   instance; optionally on the size x size grid Stage 2 trains on (ops.score_planes; summarise_instances: top-1 /
+                   best / scored / union IoU, the score-0 fragments' share of the false positives, AP by the VOC rule)
 Files are read ahead on a few host threads; consecutive names of one image share a launch pair of the map kernels (at most
 GROUP_MAX); the histograms stay on the device until a pass ends (or FLUSH names have gathered), so the host waits for the device
 less often than once per group.  The summarise_* functions are pure numpy.
@@ -141,6 +144,25 @@ def _read_masks(path, h, w):
     return np.ascontiguousarray(mask).view(np.uint8)
 
 
+def _read_instances(path, h, w):
+    """_read_masks and the file's 'score' as float64 [K]: make_ins_seg writes one per instance (0 for a fragment under 1 % of the
+    image, IRNet/step_refer/make_ins_seg_labels.py:95-101; int64 zeros where nothing was found), so integer and float dtypes both
+    pass; a missing, mis-sized or non-finite 'score' is a ValueError naming the file"""
+    stack = _read_masks(path, h, w)                    # (its checks as they are; the dict is unpickled once more for the scores)
+    rec = np.load(path, allow_pickle=True).item()
+    if "score" not in rec:
+        raise ValueError(f"{path}: the dict has no 'score' (one per instance, as make_ins_seg writes it)")
+    score = np.asarray(rec["score"])
+    if score.dtype.kind not in "iuf" or score.shape != (stack.shape[0],):
+        raise ValueError(f"{path}: 'score' is {score.dtype} {tuple(score.shape)}, expected one number for each of the "
+                         f"{stack.shape[0]} masks")
+    score = score.astype(np.float64)
+    if not np.isfinite(score).all():
+        raise ValueError(f"{path}: 'score' holds a non-finite value ({score[~np.isfinite(score)][0]}) at instance "
+                         f"{int(np.nonzero(~np.isfinite(score))[0][0])}")
+    return stack, score
+
+
 def _read_ahead(fn, jobs):
     """fn(*job) for every job, in order, READ_AHEAD of them in flight on min(16, cpu_count) threads"""
     from concurrent.futures import ThreadPoolExecutor
@@ -241,6 +263,60 @@ def score_masks(names, ins_seg_out_dir, gt, gt_rule=0):
     return out.result(), np.asarray(Ks, np.int64)
 
 
+def score_masks_train(names, ins_seg_out_dir, gt, size, gt_rule=0):
+    """score_masks on the size x size grid Stage 2 trains on: Image.NEAREST of the mask sum against Image.NEAREST of the target
+    (dataset/ReferDataset.py:178-187) read the same source pixel for an output pixel, so this is rows 0 .. 2 of ops.score_planes on
+    that grid of source pixels; neither resized image is formed.  -> (int64 [N, 3, 2], int64 [N])"""
+    import torch
+    from . import ops
+    recs = gt.of_names(names)
+    out, Ks = _Gather((3, 2)), []
+    stacks = _read_ahead(_read_masks, ((os.path.join(ins_seg_out_dir, f"{n}.npy"), r[2], r[3]) for n, r in zip(names, recs)))
+    for (lo, hi, h, w, _), stack in zip(recs, stacks):
+        Ks.append(stack.shape[0])
+        dev = torch.from_numpy(stack).to(gt.device) if stack.shape[0] else torch.empty(0, h, w, dtype=torch.uint8, device=gt.device)
+        out.add(ops.score_planes(dev, gt.arena, lo, hi, h, w, out_hw=size, gt_rule=gt_rule)[:3])
+    return out.result(), np.asarray(Ks, np.int64)
+
+
+def score_instances(names, ins_seg_out_dir, gt, size=None, gt_rule=0):
+    """per name a dict: 'table' int64 [K+3, 2], the ops.score_planes table of the whole 'mask' stack of ins_seg_out_dir/{name}.npy
+    against the name's ref (rows: sum 0, 1, above 1, then one per instance); 'scored' int64 [3, 2], rows 0 .. 2 of the planes with
+    score > 0 alone (the table's own when no score is <= 0, else a second ops.score_planes call on that sub-stack); 'K'; 'score'
+    float64 [K].  size=S: the tables of the S x S grid Stage 2 trains on (the source pixels Pillow's NEAREST resize reads)."""
+    import torch
+    from . import ops
+    recs = gt.of_names(names)
+    files = _read_ahead(_read_instances, ((os.path.join(ins_seg_out_dir, f"{n}.npy"), r[2], r[3]) for n, r in zip(names, recs)))
+    waiting, flat, scores = [], [], []
+
+    def flush():
+        if waiting:
+            flat.append(torch.cat(waiting).cpu().numpy())           # (the one wait for the device)
+            del waiting[:]
+    for (lo, hi, h, w, _), (stack, score) in zip(recs, files):
+        dev = torch.from_numpy(stack).to(gt.device) if stack.shape[0] else torch.empty(0, h, w, dtype=torch.uint8, device=gt.device)
+        table = ops.score_planes(dev, gt.arena, lo, hi, h, w, out_hw=size, gt_rule=gt_rule)
+        keep = score > 0
+        if keep.all():
+            scored = table[:3]
+        else:                                                      # (an index list from the host: no wait for the device)
+            sub = dev.index_select(0, torch.from_numpy(np.nonzero(keep)[0]).to(gt.device))
+            scored = ops.score_planes(sub, gt.arena, lo, hi, h, w, out_hw=size, gt_rule=gt_rule)[:3]
+        waiting += [table, scored]
+        scores.append(score)
+        if len(waiting) >= 2 * FLUSH:
+            flush()
+    flush()
+    flat = np.concatenate(flat) if flat else np.zeros((0, 2), np.int64)
+    out, at = [], 0
+    for score in scores:
+        K = score.size
+        out.append({"table": flat[at:at + K + 3], "scored": flat[at + K + 3:at + K + 6], "K": K, "score": score})
+        at += K + 6
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------ numbers
 def _ratio(num, den):
     return float(num) / float(den) if den > 0 else None
@@ -307,3 +383,116 @@ def summarise_masks(hist3, K):
     t = h.sum(0)
     return {"names": int(h.shape[0]), "mIoU": miou, "oIoU": oiou, "overlap_share": _ratio(t[2].sum(), t[1:].sum()),
             "mean_K": _ratio(K.sum(), K.size), "empty_share": _ratio((K == 0).sum(), K.size)}
+
+
+# ------------------------------------------------------------------------------------------------------------------ instances
+AP_THRESHOLDS_20 = tuple(range(10, 20))          # tau = q/20: 0.50, 0.55 ... 0.95
+
+
+def instance_counts(rec):
+    """one record of score_instances -> (a, i, g): a[k] the area of instance k, i[k] its intersection with the ground truth (Python
+    integers), g the ground-truth area"""
+    t = np.asarray(rec["table"], np.int64)
+    return [int(v) for v in t[3:].sum(1)], [int(v) for v in t[3:, 1]], int(t[:3, 1].sum())
+
+
+def _voc_ap(dets, n_pos, q):
+    """dets in rank order: (name, a, i, g).  True positive: g > 0, 20 i >= q (a + g - i), and the first such of its name.  The area
+    under the precision envelope over recall (all-point interpolation); None without a positive name."""
+    if n_pos == 0:
+        return None
+    hit, tp, fp, curve = set(), 0, 0, []
+    for name, a, i, g in dets:
+        if g > 0 and 20 * i >= q * (a + g - i) and name not in hit:
+            hit.add(name)
+            tp += 1
+        else:
+            fp += 1
+        curve.append((tp, tp + fp))
+    ap, best = 0.0, 0.0
+    for j in range(len(curve) - 1, -1, -1):                        # the envelope from the right: max precision at this recall or beyond
+        best = max(best, curve[j][0] / curve[j][1])
+        if curve[j][0] > (curve[j - 1][0] if j else 0):            # recall rises by 1/n_pos here
+            ap += best / n_pos
+    return ap
+
+
+def pick_top1(score):
+    """the instance of highest score, the first on ties; None without instances"""
+    top = None
+    for k in range(len(score)):
+        if top is None or score[k] > score[top]:
+            top = k
+    return top
+
+
+def pick_best(a, i, g):
+    """the instance of highest IoU = i / (a + g - i), the first on ties; None without instances.  Python integers, compared by
+    cross-multiplication: i_k u_b > i_b u_k (u = 0 only with i = 0, which then counts as an IoU of 0 on either side)"""
+    best = None
+    for k in range(len(a)):
+        if best is None or i[k] * (a[best] + g - i[best]) > i[best] * (a[k] + g - i[k]):
+            best = k
+    return best
+
+
+def summarise_instances(recs):
+    """the records of score_instances -> dict.  A project definition (the reference names --eval_ins_seg_pass and ships no such pass):
+    per instance IoU = i / (a + g - i), 0 where that is 0.  Four ways to turn a name's instances into one mask, each as mIoU / oIoU:
+    top1 (the highest score, the first on ties), best (the highest IoU, compared as exact fractions, the first on ties), scored (the
+    union of the planes with score > 0), union (all planes: the 'masks' numbers).  K = 0: I = 0, U = g.  zero_score_share = the
+    share of instances with score <= 0, zero_score_fp_share = their share of sum (a - i); a ratio with a zero denominator is None.
+    ap50 / ap75 / ap (the mean over 0.50, 0.55 ... 0.95): the VOC detection rule restated, one ground-truth object per name --
+    detections by score descending (float64; ties by the name's position, then the plane), a true positive iff g > 0, IoU >= tau in
+    integers and no earlier one of its name, all-point interpolation, None when no name has g > 0."""
+    I = {k: [] for k in ("top1", "best", "scored", "union")}
+    U = {k: [] for k in I}
+    dets, n_pos, n_inst, n_zero, fp_all, fp_zero = [], 0, 0, 0, 0, 0
+    for n, rec in enumerate(recs):
+        a, i, g = instance_counts(rec)
+        score = [float(s) for s in rec["score"]]
+        assert len(a) == len(score) == rec["K"], (len(a), len(score), rec["K"])
+        n_pos += g > 0
+        top, best = pick_top1(score), pick_best(a, i, g)
+        for k in range(len(a)):
+            dets.append((-score[k], n, k, a[k], i[k], g))
+            n_inst += 1
+            fp_all += a[k] - i[k]
+            if score[k] <= 0:
+                n_zero += 1
+                fp_zero += a[k] - i[k]
+        for key, k in (("top1", top), ("best", best)):
+            I[key].append(0 if k is None else i[k])
+            U[key].append(g if k is None else a[k] + g - i[k])
+        for key, h in (("scored", rec["scored"]), ("union", np.asarray(rec["table"])[:3])):
+            pi, pu = masks_iu(np.asarray(h, np.int64)[None])
+            I[key].append(int(pi[0]))
+            U[key].append(int(pu[0]))
+    out = {"names": len(recs), "instances": n_inst}
+    for key in ("top1", "best", "scored", "union"):
+        m, o = _miou_oiou(np.asarray(I[key], np.int64), np.asarray(U[key], np.int64))
+        out[key] = {"mIoU": m, "oIoU": o}
+    out["zero_score_share"] = _ratio(n_zero, n_inst)
+    out["zero_score_fp_share"] = _ratio(fp_zero, fp_all)
+    dets.sort(key=lambda d: d[:3])
+    ranked = [(n, a, i, g) for _, n, _, a, i, g in dets]
+    aps = [_voc_ap(ranked, n_pos, q) for q in AP_THRESHOLDS_20]
+    out["n_pos"] = int(n_pos)
+    out["ap50"], out["ap75"] = aps[0], aps[5]
+    out["ap"] = None if n_pos == 0 else sum(aps) / len(aps)
+    return out
+
+
+def instance_arrays(recs):
+    """the per-instance integers of all names, flat: inst_offsets int64 [N+1], inst_score float64, inst_area, inst_inter int64 (the
+    instances of name n are offsets[n] .. offsets[n+1]-1), inst_gt_area int64 [N]"""
+    off, score, area, inter, gts = [0], [], [], [], []
+    for rec in recs:
+        a, i, g = instance_counts(rec)
+        off.append(off[-1] + len(a))
+        score += [float(s) for s in rec["score"]]
+        area += a
+        inter += i
+        gts.append(g)
+    return {"inst_offsets": np.asarray(off, np.int64), "inst_score": np.asarray(score, np.float64),
+            "inst_area": np.asarray(area, np.int64), "inst_inter": np.asarray(inter, np.int64), "inst_gt_area": np.asarray(gts, np.int64)}
