@@ -272,7 +272,7 @@ def _steps(arith, graph, B=3, steps=3):
                     torch.cuda.synchronize()
                     g1 = [a.g.clone() for a in opt.arenas]
             torch.cuda.synchronize()
-            return torch.stack(losses), g1, ops._H2["next"]
+            return torch.stack(losses), g1, ops._H2.next
     finally:
         ops.set_gemm_mode(prev)
 

@@ -690,12 +690,12 @@ def test_tower_survives_an_amax_pool_restart_inside_the_packed_pass(aux):
             ref = padded(aux, A)
             O.h2_begin_step()
             O.h2_end_step()
-            while O._H2["next"] < O.H2_SLOTS - 40:
+            while O._H2.next < O.H2_SLOTS - 40:
                 O._h2_slot()
-            step = O._H2["step"]
+            step = O._H2.step
             hit = poison()
             got = aux.encode_text_hidden(A)
-            assert O._H2["step"] != step          # (the pool did restart inside the pass)
+            assert O._H2.step != step          # (the pool did restart inside the pass)
             rel = rel_err(got, ref)
             print(f"pool restart inside the packed pass: max err / max |ref| = {rel:.3e}; poisoned torch.empty came back NaN: {hit}")
             assert bool(torch.isfinite(got).all()) and rel <= TOWER_TOL

@@ -321,17 +321,17 @@ def test_two_forwards_then_one_backward_outside_an_explicit_step(ops):
     wv = torch.linspace(-1, 1, 256, device="cuda")
 
     def fwd(net, x):
-        assert ops.h2_auto_step() or ops._H2["next"] == ops._H2.get("base", -1)
+        assert ops.h2_auto_step() or ops._H2.next == ops._H2.base
         return (ops.unplanes(net(x)) * wv).sum()
     net = _stack(3)
     ops.h2_end_step()
-    ops._H2["next"] = ops._H2.get("base", 0) + 1          # (something was handed out since the last begin: the next forward starts a step)
+    ops._H2.next = max(ops._H2.base, 0) + 1          # (something was handed out since the last begin: the next forward starts a step)
     before = dict(ops.PL_STATS)
     x1, x2 = xa.clone().requires_grad_(), xb.clone().requires_grad_()
     l1 = fwd(net, x1)
-    step1 = ops._H2["step"]
+    step1 = ops._H2.step
     l2 = fwd(net, x2)
-    assert ops._H2["step"] != step1 and step1 in ops._H2["auto_pools"]      # a pool each; the first one retired, alive
+    assert ops._H2.step != step1 and step1 in ops._H2.auto_pools      # a pool each; the first one retired, alive
     (l1 + l2).backward()
     torch.cuda.synchronize()
     d = {k: ops.PL_STATS[k] - before[k] for k in before if not k.startswith("last")}
@@ -354,7 +354,7 @@ def test_two_forwards_then_one_backward_outside_an_explicit_step(ops):
         assert float((got[2][n_] - ref_g[n_]).norm() / ref_g[n_].norm().clamp_min(1e-12)) < 5e-5, n_
     # a fifth-oldest forward's planes are gone (H2_AUTO_KEEP retired pools), and an explicit step drops them all
     ops.h2_begin_step()
-    assert not ops._H2["auto_pools"]
+    assert not ops._H2.auto_pools
     ops.h2_end_step()
 
 

@@ -417,7 +417,7 @@ def _word_of(ops, t):
     slot = ops._h2_tag_slot(t)
     if slot is None:
         return None
-    pool = ops._H2["pool"]
+    pool = ops._H2.pool
     i = (slot - pool.data_ptr()) // 4
     return pool[i:i + ops.H2_SUB]
 

@@ -17,7 +17,7 @@ for (N, L, heads, causal, what) in ((48, 401, 12, False, "ViT-B/16 trunk, 320 px
     def tag(t):   # what the producing product does in the step: leave the tensor's amax word behind
         slot = ops._h2_slot()
         ops.call("tris_amax_bits_f32", ops.P(t), t.numel(), slot, ops._stream())
-        t._h2 = (ops._H2["step"], slot, t._version)
+        ops.h2_tag(t, slot)
     for form in ("f32", "h2"):
         cfg.mha_h2, cfg.mha = form == "h2", "mfma"
         qkv = qkv0.clone().requires_grad_(True)

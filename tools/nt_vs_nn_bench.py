@@ -11,7 +11,7 @@ ops.set_autotune(True)
 def tag(t):
     slot = ops._h2_slot()
     ops.call("tris_amax_bits_f32", ops.P(t), t.numel(), slot, ops._stream())
-    t._h2 = (ops._H2["step"], slot, t._version)
+    ops.h2_tag(t, slot)
 
 
 for (M, Nout, Kin, what) in ((19248, 3072, 768, "ViT-B/16 c_fc dgrad"), (19248, 768, 3072, "ViT-B/16 c_proj dgrad"),
@@ -21,7 +21,7 @@ for (M, Nout, Kin, what) in ((19248, 3072, 768, "ViT-B/16 c_fc dgrad"), (19248, 
     dY = torch.randn(M, Nout, generator=g).cuda()
     W = (torch.randn(Nout, Kin, generator=g) * 0.05).cuda()
     Wt = W.t().contiguous()
-    tag(dY); tag(W); Wt._h2 = W._h2
+    tag(dY); tag(W); ops.h2_tag(Wt, W._h2.word)
     dX = torch.empty(M, Kin, device="cuda")
     res = {}
     for form in ("NN", "NT"):

@@ -306,7 +306,7 @@ class SegmentedTrainStep:
 
         self.h2_pool = ops.h2_begin_step()   # (h2 arithmetic: the amax pool the captured launches write; zeroed per replay)
         self.h2_aux = ops.h2_private_pool()  # (the frozen aux text tower's own words: its graph clears them itself)
-        self.h2_arenas = list(ops._H2.get("arenas", [])) if self.h2_pool is not None else []
+        self.h2_arenas = ops.h2_step_arenas() if self.h2_pool is not None else []
         # No garbage collection while streams are capturing: a collection that runs in the middle (any thread -- the autograd engine
         # executes Python too) may destroy hipGraphs / free pool memory of an earlier captured step, which is illegal on a capturing
         # thread and aborts the process.  Collect first, then keep the collector off until the last capture has ended.

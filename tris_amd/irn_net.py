@@ -306,7 +306,7 @@ class EdgeDisplacement(nn.Module):
         self._prepare(img.device)
         self.calls += 1
         with ops.autotune_off():
-            if ops.h2_on() and not ops._H2.get("in_step") and not ops._H2.get("private"):
+            if ops.h2_on() and not ops.h2_step_open():
                 ops.h2_begin_step(explicit=False)     # a fresh amax pool: the pass never straddles two
             t = self._trunk(self._stem(img))
             y = self.heads(t)

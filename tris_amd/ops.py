@@ -14,7 +14,9 @@ see tris_amd.optim).  Backward kernels then write the weight gradient straight i
 """
 import ctypes
 import math
+import contextlib
 import os
+import weakref
 from typing import NamedTuple, Optional
 
 import torch
@@ -487,13 +489,13 @@ class batch_invariant:
         # rows share the launch, so h2 cannot be batch-invariant (measured in round 6: one of 128 hit-tests flipped between group
         # sizes).  Inside this scope products run in the split-bf16 x3 arithmetic -- exact pieces, no data-dependent scale, row results
         # independent of the batch -- which is also the faster one at evaluation sizes (no amax words to produce or read).
-        _H2["paused"] += 1
+        _H2.paused += 1
         return self
 
     def __exit__(self, *exc):
         global _BATCH_INVARIANT
         _BATCH_INVARIANT -= 1
-        _H2["paused"] -= 1
+        _H2.paused -= 1
         if _BATCH_INVARIANT == 0:
             call("tris_set_conv_direct_thread", -1)
         return False
@@ -717,8 +719,38 @@ class GradBox:
 # A product whose operands have no amax runs in x3.  A "step" is the life of the pool's words: h2_begin_step() clears the pool
 # (train_step calls it; any other entry -- an evaluation forward, a lone op in a test -- starts one on first use or when the pool
 # is full).
-_H2 = {"pool": None, "next": 0, "step": 0, "paused": 0, "arenas": [], "const": None, "const_next": 0, "const_tags": {}}
+class _H2State:
+    """the state of the amax pools: one instance, _H2, every field declared here with its default"""
+    __slots__ = ("pool", "next", "base", "step", "paused", "in_step", "auto_lock", "auto_grad", "auto_pools", "private", "limit", "arenas",
+                 "plane_numel", "const", "const_next", "const_tags")
+
+    def __init__(self):
+        self.pool, self.next, self.base, self.step = None, 0, -1, 0   # the step's words, the next one to hand out, the first one behind the arenas', the step id
+        self.paused = 0                                               # depth of h2_paused / batch_invariant scopes
+        self.in_step = self.auto_lock = self.auto_grad = False        # inside an explicit step / h2_auto_lock; the step is a gradient-mode forward's own
+        self.auto_pools = {}                                          # step id -> retired pool, oldest first (H2_AUTO_KEEP)
+        self.private, self.limit = False, None                        # inside h2_private_pool, and its number of words
+        self.arenas, self.plane_numel = [], {}                        # the arenas the step tagged; word -> elements of the plane tensors written in it
+        self.const, self.const_next, self.const_tags = None, 0, {}    # the constant words: id(parameter) -> _ConstWord
+
+    def swap(self, **new):
+        """set the fields named -> what restore() puts back: those fields and no other"""
+        saved = {k: getattr(self, k) for k in new}
+        self.restore(new)
+        return saved
+
+    def restore(self, saved):
+        for k, v in saved.items():
+            setattr(self, k, v)
+
+
+_H2 = _H2State()
 _H2_STEP_IDS = [0]       # step ids are unique across the main pool and private pools: a tag never matches another pool's step
+# What rides on tensors and parameters.  Each is written in ONE place: t._h2 by h2_tag, t._pl by pl_tag, p._plw / p._plwt by h2_begin_step
+_AmaxTag = NamedTuple("_AmaxTag", [("step", int), ("word", int), ("version", int)])          # t._h2: t's amax is in `word` while t is unwritten
+_PlaneTag = NamedTuple("_PlaneTag", [("step", int), ("word", int), ("ptr", int)])            # t._pl: t's bytes are planes scaled by `word`
+_WeightPlanes = NamedTuple("_WeightPlanes", [("step", int), ("ptr", int), ("word", int)])    # p._plw / p._plwt: an arena parameter's (transposed) planes
+_PlaneGrad = NamedTuple("_PlaneGrad", [("step", int), ("word", int), ("shape", tuple)])      # _PL_GRAD entries
 H2_SLOTS = 4096          # amax words per step; a word is H2_SUB unsigned words (csrc/amax.h amax_raise)
 H2_SUB = 2048
 H2_CONST_SLOTS = 1024
@@ -727,7 +759,7 @@ H2_AUTO_KEEP = 4         # retired pools of gradient-mode forwards issued outsid
 
 
 def h2_on():
-    return _ARITH == "h2" and not _H2["paused"] and not _thread_mode_is_set()
+    return _ARITH == "h2" and not _H2.paused and not _thread_mode_is_set()
 
 
 _H2_ARENAS = []   # weak references to the optimiser arenas whose parameters get their amax from ONE launch per step
@@ -736,7 +768,6 @@ _H2_ARENAS = []   # weak references to the optimiser arenas whose parameters get
 def h2_register_arena(arena):
     """an optimiser arena (tris_amd.optim.Arena: .p flat parameter buffer, .params, .offsets).  Its parameters are updated in
     place by kernels that do not bump torch's version counters, so they never get a CONSTANT amax word (_h2_const_slot)."""
-    import weakref
     r = weakref.ref(arena)
     _H2_ARENAS.append(r)
     for p in arena.params:
@@ -751,46 +782,51 @@ def _h2_live_arenas():
         a = r()
         if a is None or not a.params or getattr(a.params[0], "_tris_arena", None) is not r:
             _H2_ARENAS.remove(r)
-        elif _H2["pool"] is not None and a.p.device == _H2["pool"].device and words + len(a.params) <= H2_SLOTS // 2:
+        elif _H2.pool is not None and a.p.device == _H2.pool.device and words + len(a.params) <= H2_SLOTS // 2:
             out.append(a)
             words += len(a.params)
     return out
 
 
-def h2_weights_amax(arenas=None):
-    """(re)compute the amax words of the arenas' parameters: the first words of the pool, in order.  arenas: the list a
-    captured step recorded (its launches read those words); default: the live registered ones"""
+# _ArenaPlanes: the parameters of an optimiser arena that exist as operand planes too (csrc/planes.h) -- `idx` --, their segment tables on the
+# device and the plane buffer (None: no such parameter).  _ArenaWords: what the per-step launches of one arena read, built once per arena:
+# the offsets and sizes of its parameters on the device and, from the first step with operand planes on, the planes of its convolution
+# weights (`pl`) and of its 1x1 weights TRANSPOSED (`plt`: their data gradient dX = dY . W is then the forward's row-major A x B^T product)
+_ArenaPlanes = NamedTuple("_ArenaPlanes", [("idx", list), ("seg", tuple), ("buf", Optional[torch.Tensor]), ("attr", str)])
+_ArenaWords = NamedTuple("_ArenaWords", [("seg", tuple), ("pl", Optional[_ArenaPlanes]), ("plt", Optional[_ArenaPlanes])])
+_ARENA_WORDS = weakref.WeakKeyDictionary()
+
+
+def _arena_words(a):
+    mk = lambda v: torch.tensor(v, device=a.p.device, dtype=torch.int64)
+    planes = lambda attr, idx, *cols: _ArenaPlanes(idx, tuple(mk([c(i) for i in idx]) for c in cols) if idx else None,
+                                                   torch.zeros_like(a.p) if idx else None, attr)
+    r = _ARENA_WORDS.get(a) or _ArenaWords((mk(list(a.offsets)), mk([p.numel() for p in a.params])), None, None)
+    if r.pl is None and cfg.h2_planes:
+        idx = [i for i, p in enumerate(a.params) if _pl_weight_ok(p)]
+        idt = [i for i in idx if _pl_weight_t_ok(a.params[i])]
+        r = r._replace(pl=planes("_plw", idx, lambda i: a.offsets[i], lambda i: a.params[i].numel(), lambda i: i),
+                       plt=planes("_plwt", idt, lambda i: a.offsets[i], lambda i: a.params[i].shape[0], lambda i: a.params[i].shape[1], lambda i: i))
+    _ARENA_WORDS[a] = r
+    return r
+
+
+def h2_weights_amax(arenas=None, tag=False):
+    """(re)compute the amax words of the arenas' parameters -- the first words of the pool, in order -- and with them their planes: for
+    each arena its record, then up to three launches.  arenas: the list a captured step recorded (its launches read those words);
+    default: the live registered ones.  tag (h2_begin_step): the parameters are tagged with their words and planes.  -> the words used"""
     base = 0
     for a in (_h2_live_arenas() if arenas is None else arenas):
-        if not hasattr(a, "_h2_dev"):
-            a._h2_dev = (torch.tensor(list(a.offsets), device=a.p.device, dtype=torch.int64),
-                         torch.tensor([p.numel() for p in a.params], device=a.p.device, dtype=torch.int64))
-        call("tris_amax_segments_f32", P(a.p), a._h2_dev[0].data_ptr(), a._h2_dev[1].data_ptr(), len(a.params),
-             _H2["pool"].data_ptr() + 4 * H2_SUB * base, _stream())
-        if cfg.h2_planes:
-            # operand planes of the convolution weights (csrc/planes.h), refreshed with the amaxes: one more launch per arena
-            if not hasattr(a, "_pl_dev"):
-                idx = [i for i, p in enumerate(a.params) if _pl_weight_ok(p)]
-                a._pl_idx = idx
-                a._pl_dev = None if not idx else (
-                    torch.tensor([a.offsets[i] for i in idx], device=a.p.device, dtype=torch.int64),
-                    torch.tensor([a.params[i].numel() for i in idx], device=a.p.device, dtype=torch.int64),
-                    torch.tensor(idx, device=a.p.device, dtype=torch.int64))
-                a.pl = torch.zeros_like(a.p) if idx else None
-            if a._pl_dev is not None:
-                call("tris_h2_planes_segments_f32", P(a.p), a._pl_dev[0].data_ptr(), a._pl_dev[1].data_ptr(), a._pl_dev[2].data_ptr(),
-                     len(a._pl_idx), _H2["pool"].data_ptr() + 4 * H2_SUB * base, P(a.pl), _stream())
-            # ... and of the 1x1 weights TRANSPOSED: their data gradient dX = dY . W is then the forward's row-major A x B^T product
-            if not hasattr(a, "_plt_dev"):
-                idt = [i for i in getattr(a, "_pl_idx", []) if _pl_weight_t_ok(a.params[i])]
-                a._plt_idx = idt
-                mk = lambda v: torch.tensor(v, device=a.p.device, dtype=torch.int64)
-                a._plt_dev = None if not idt else (mk([a.offsets[i] for i in idt]), mk([a.params[i].shape[0] for i in idt]),
-                                                   mk([a.params[i].shape[1] for i in idt]), mk(idt))
-                a.plt = torch.zeros_like(a.p) if idt else None
-            if a._plt_dev is not None:
-                call("tris_h2_planes_t_segments_f32", P(a.p), a._plt_dev[0].data_ptr(), a._plt_dev[1].data_ptr(), a._plt_dev[2].data_ptr(),
-                     a._plt_dev[3].data_ptr(), len(a._plt_idx), _H2["pool"].data_ptr() + 4 * H2_SUB * base, P(a.plt), _stream())
+        r, words = _arena_words(a), _H2.pool.data_ptr() + 4 * H2_SUB * base
+        call("tris_amax_segments_f32", P(a.p), *(t.data_ptr() for t in r.seg), len(a.params), words, _stream())
+        for pl, entry in ((r.pl, "tris_h2_planes_segments_f32"), (r.plt, "tris_h2_planes_t_segments_f32")) if cfg.h2_planes else ():
+            if pl.idx:
+                call(entry, P(a.p), *(t.data_ptr() for t in pl.seg), len(pl.idx), words, P(pl.buf), _stream())
+            for i in (pl.idx if tag else ()):
+                setattr(a.params[i], pl.attr, _WeightPlanes(_H2.step, pl.buf.data_ptr() + 4 * a.offsets[i], words + 4 * H2_SUB * i))
+                _H2.plane_numel[words + 4 * H2_SUB * i] = a.params[i].numel()
+        for i, p in enumerate(a.params if tag else ()):
+            h2_tag(p, words + 4 * H2_SUB * i)
         base += len(a.params)
     return base
 
@@ -836,54 +872,65 @@ def h2_begin_step(explicit=True):
     current stream first waits for the side streams.  explicit: the caller brackets a whole step (h2_end_step closes it)."""
     if _ARITH != "h2":
         return None
-    _H2["in_step"] = bool(explicit)
+    _H2.in_step = bool(explicit)
     wgrad_join()
     dev = torch.device("cuda", torch.cuda.current_device())
     # A forward issued OUTSIDE an explicit step with gradients on may still have its autograd graph -- and the plane tensors saved in
     # it -- alive when the next such forward begins (gradient accumulation, a drop-in user summing the losses of two forwards before
     # one backward: legal PyTorch).  Its pool is then RETIRED, not cleared: the words stay what the saved plane tensors were written
     # under (pl_word accepts the H2_AUTO_KEEP most recent retired steps) and the new forward gets a fresh pool.
-    live = _H2.setdefault("auto_pools", {})
-    if _H2["pool"] is None or _H2["pool"].device != dev:
-        _H2["pool"] = torch.zeros(H2_SLOTS * H2_SUB, device=dev, dtype=torch.int32)
+    live = _H2.auto_pools
+    if _H2.pool is None or _H2.pool.device != dev:
+        _H2.pool = torch.zeros(H2_SLOTS * H2_SUB, device=dev, dtype=torch.int32)
         live.clear()
-    elif not explicit and _H2.get("auto_grad") and not _H2.get("private") and not torch.cuda.is_current_stream_capturing():
-        live[_H2["step"]] = _H2["pool"]
+    elif not explicit and _H2.auto_grad and not _H2.private and not torch.cuda.is_current_stream_capturing():
+        live[_H2.step] = _H2.pool
         while len(live) > H2_AUTO_KEEP:
             live.pop(next(iter(live)))
-        _H2["pool"] = torch.zeros(H2_SLOTS * H2_SUB, device=dev, dtype=torch.int32)
+        _H2.pool = torch.zeros(H2_SLOTS * H2_SUB, device=dev, dtype=torch.int32)
     else:
         if explicit:
             live.clear()
-        _H2["pool"].zero_()
-    _H2["auto_grad"] = (not explicit) and torch.is_grad_enabled() and not _H2.get("private")
-    _H2["step"] = _h2_new_step_id()
-    _H2["plane_numel"] = {}
+        _H2.pool.zero_()
+    _H2.auto_grad = (not explicit) and torch.is_grad_enabled() and not _H2.private
+    _H2.step = _h2_new_step_id()
+    _H2.plane_numel = {}
     _PL_GRAD.clear()
-    base = 0
-    arenas = _h2_live_arenas() if not _H2.get("private") else []
-    for a in arenas:
-        for i, p in enumerate(a.params):
-            p._h2 = (_H2["step"], _H2["pool"].data_ptr() + 4 * H2_SUB * (base + i), p._version)
-        base += len(a.params)
-    _H2["next"] = _H2["base"] = base
-    _H2["arenas"] = arenas
-    h2_weights_amax(arenas)
-    if cfg.h2_planes:
-        for a in arenas:
-            for i in (a._pl_idx if getattr(a, "pl", None) is not None else ()):
-                p = a.params[i]
-                p._plw = (_H2["step"], a.pl.data_ptr() + 4 * a.offsets[i], p._h2[1])
-                _H2["plane_numel"][p._h2[1]] = p.numel()
-            for i in (a._plt_idx if getattr(a, "plt", None) is not None else ()):
-                p = a.params[i]
-                p._plwt = (_H2["step"], a.plt.data_ptr() + 4 * a.offsets[i], p._h2[1])
-    return _H2["pool"]
+    _H2.arenas = _h2_live_arenas() if not _H2.private else []
+    _H2.next = _H2.base = h2_weights_amax(_H2.arenas, tag=True)
+    return _H2.pool
 
 
 def h2_end_step():
     """the explicit step ends: the words stay valid until the next begin; forwards issued outside a step start their own again"""
-    _H2["in_step"] = False
+    _H2.in_step = False
+
+
+def h2_step_open():
+    """inside an explicit step or a private pool: whoever asks must not begin a step of its own"""
+    return _H2.in_step or _H2.private
+
+
+def h2_step_arenas():
+    """the arenas whose parameters the open step tagged (a captured step keeps them for h2_weights_amax)"""
+    return list(_H2.arenas)
+
+
+def h2_pool_state():
+    """a snapshot for tools/h2_step_trace.py: where the pools lie (the retired ones oldest first), the hand-out counters and the step id"""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return {"pool": ptr(_H2.pool), "retired": [ptr(p) for p in _H2.auto_pools.values()], "const": ptr(_H2.const), "private": _H2.private,
+            "limit": _H2.limit, "next": _H2.next, "base": _H2.base, "step": _H2.step}
+
+
+@contextlib.contextmanager
+def h2_fresh_consts():
+    """a scope with a pool of constant words of its own (launch traces: which word a parameter gets does not depend on what ran before)"""
+    saved = _H2.swap(const=None, const_next=0, const_tags={})
+    try:
+        yield
+    finally:
+        _H2.restore(saved)
 
 
 def h2_auto_step():
@@ -893,9 +940,9 @@ def h2_auto_step():
     of running into a half-used pool that restarts mid-way.  No-op inside an explicit step, when planes are off, and when nothing
     has been handed out since the last begin.  Returns True if a step was begun (the caller's nested forwards must not begin another:
     h2_auto_lock)."""
-    if not planes_on() or _H2.get("in_step") or _H2.get("auto_lock") or _H2.get("private"):
+    if not planes_on() or _H2.in_step or _H2.auto_lock or _H2.private:
         return False
-    if _H2["pool"] is not None and _H2["next"] == _H2.get("base", -1):
+    if _H2.pool is not None and _H2.next == _H2.base:
         return False
     h2_begin_step(explicit=False)
     return True
@@ -905,11 +952,11 @@ class h2_auto_lock:
     """inside: nested forwards do not begin a step of their own (TRIS.forward around its trunk call)"""
 
     def __enter__(self):
-        self.prev = _H2.get("auto_lock", False)
-        _H2["auto_lock"] = True
+        self.prev = _H2.auto_lock
+        _H2.auto_lock = True
 
     def __exit__(self, *a):
-        _H2["auto_lock"] = self.prev
+        _H2.auto_lock = self.prev
 
 
 class h2_step:
@@ -921,7 +968,7 @@ class h2_step:
         self.explicit, self.mine = explicit, False
 
     def __enter__(self):
-        self.mine = h2_on() and not _H2.get("in_step") and not _H2.get("private")
+        self.mine = h2_on() and not h2_step_open()
         if self.mine:
             h2_begin_step(explicit=self.explicit)
         return self
@@ -944,12 +991,11 @@ class h2_private_pool:
         self.active = _ARITH == "h2"
         if not self.active:
             return self
-        self.saved = {k: _H2.get(k) for k in ("pool", "next", "step", "arenas", "private", "limit")}
         dev = torch.device("cuda", torch.cuda.current_device())
         if self.pool is None or self.pool.device != dev:
             self.pool = torch.zeros(self.slots * H2_SUB, device=dev, dtype=torch.int32)
-        _H2.update(pool=self.pool, arenas=[], private=True, limit=self.slots)
-        self.reset()
+        self.pool.zero_()
+        self.saved = _H2.swap(pool=self.pool, next=0, step=_h2_new_step_id(), arenas=[], private=True, limit=self.slots)
         return self
 
     def reset(self):
@@ -957,11 +1003,11 @@ class h2_private_pool:
         memset is then part of the graph, and the words are handed out in the same order at every recording)"""
         if self.active:
             self.pool.zero_()
-            _H2.update(next=0, step=_h2_new_step_id())
+            _H2.next, _H2.step = 0, _h2_new_step_id()
 
     def __exit__(self, *exc):
         if self.active:
-            _H2.update(self.saved)
+            _H2.restore(self.saved)
         return False
 
 
@@ -969,21 +1015,21 @@ class h2_paused:
     """products launched inside run in x3"""
 
     def __enter__(self):
-        _H2["paused"] += 1
+        _H2.paused += 1
 
     def __exit__(self, *a):
-        _H2["paused"] -= 1
+        _H2.paused -= 1
 
 
 def _h2_slot():
-    limit = _H2.get("limit") or H2_SLOTS
-    if _H2["pool"] is None or (_H2["next"] >= limit and not _H2.get("private")):
-        h2_begin_step(explicit=bool(_H2.get("in_step")))          # first use outside a training step, or the pool is full: a new step
-    i = _H2["next"]
+    limit = _H2.limit or H2_SLOTS
+    if _H2.pool is None or (_H2.next >= limit and not _H2.private):
+        h2_begin_step(explicit=_H2.in_step)          # first use outside a training step, or the pool is full: a new step
+    i = _H2.next
     if i >= limit:
         return None              # (a private pool is never restarted: its region would lose words it still reads)
-    _H2["next"] = i + 1
-    return _H2["pool"].data_ptr() + 4 * H2_SUB * i
+    _H2.next = i + 1
+    return _H2.pool.data_ptr() + 4 * H2_SUB * i
 
 
 def h2_mark_next(t):
@@ -995,41 +1041,53 @@ def h2_mark_next(t):
     if slot is None:
         return
     call("tris_amax_next", slot)
-    t._h2 = (_H2["step"], slot, t._version)
+    h2_tag(t, slot)
+
+
+def h2_tag(t, word, step=None):
+    """THE writer of t._h2: t's amax is in `word` of the running step (step: of that one -- a tag put back) until t is written to"""
+    t._h2 = _AmaxTag(_H2.step if step is None else step, word, t._version)
 
 
 def _h2_tag_slot(t):
     tag = getattr(t, "_h2", None)
-    if tag is not None and tag[0] == _H2["step"] and tag[2] == t._version:
-        return tag[1]
+    if tag is not None and tag.step == _H2.step and tag.version == t._version:
+        return tag.word
     return None
+
+
+# The two caches of parameters outside the optimiser arenas, both keyed by id(parameter): its constant amax word and its planes
+_ConstWord = NamedTuple("_ConstWord", [("version", int), ("ptr", int), ("word", int), ("ref", weakref.ref)])
+_ConstPlanes = NamedTuple("_ConstPlanes", [("version", int), ("ptr", int), ("word", int), ("planes", torch.Tensor), ("ref", weakref.ref)])
+
+
+def _still_is(entry, t):
+    """is this cache entry (of id(t)) still THIS live parameter at this address?  (an id is handed out again once its object is gone)"""
+    return entry is not None and entry.ptr == t.data_ptr() and entry.ref() is t
 
 
 def _h2_const_slot(t):
     """amax word of a parameter outside the optimiser arenas (a frozen model's): computed once, valid until it is written to"""
-    key = id(t)
-    tag = _H2["const_tags"].get(key)
-    if tag is not None and tag[1] == t.data_ptr() and tag[3]() is t and _H2["const"] is not None and _H2["const"].device == t.device:
-        if tag[0] == t._version:
-            return tag[2]
-        # written to since (load_state_dict, seed_fill): refresh the SAME word on the stream -- a hipGraph that recorded its address
-        # (the frozen aux text tower, the evaluation graphs) goes on reading a valid amax, and no new slot is used up
-        i = (tag[2] - _H2["const"].data_ptr()) // (4 * H2_SUB)
-        _H2["const"][i * H2_SUB:(i + 1) * H2_SUB].zero_()
-        call("tris_amax_bits_f32", P(t), t.numel(), tag[2], _stream())
-        _H2["const_tags"][key] = (t._version, t.data_ptr(), tag[2], tag[3])
-        return tag[2]
-    if _H2["const"] is None or _H2["const"].device != t.device:
-        _H2["const"] = torch.zeros(H2_CONST_SLOTS * H2_SUB, device=t.device, dtype=torch.int32)
-        _H2["const_next"] = 0
-        _H2["const_tags"].clear()
-    if _H2["const_next"] >= H2_CONST_SLOTS:
+    tag = _H2.const_tags.get(id(t))
+    if _still_is(tag, t) and _H2.const is not None and _H2.const.device == t.device:
+        if tag.version != t._version:
+            # written to since (load_state_dict, seed_fill): refresh the SAME word on the stream -- a hipGraph that recorded its address
+            # (the frozen aux text tower, the evaluation graphs) goes on reading a valid amax, and no new slot is used up
+            i = (tag.word - _H2.const.data_ptr()) // (4 * H2_SUB)
+            _H2.const[i * H2_SUB:(i + 1) * H2_SUB].zero_()
+            call("tris_amax_bits_f32", P(t), t.numel(), tag.word, _stream())
+            _H2.const_tags[id(t)] = tag._replace(version=t._version)
+        return tag.word
+    if _H2.const is None or _H2.const.device != t.device:
+        _H2.const = torch.zeros(H2_CONST_SLOTS * H2_SUB, device=t.device, dtype=torch.int32)
+        _H2.const_next = 0
+        _H2.const_tags.clear()
+    if _H2.const_next >= H2_CONST_SLOTS:
         return None
-    import weakref
-    slot = _H2["const"].data_ptr() + 4 * H2_SUB * _H2["const_next"]
-    _H2["const_next"] += 1
+    slot = _H2.const.data_ptr() + 4 * H2_SUB * _H2.const_next
+    _H2.const_next += 1
     call("tris_amax_bits_f32", P(t), t.numel(), slot, _stream())
-    _H2["const_tags"][key] = (t._version, t.data_ptr(), slot, weakref.ref(t))
+    _H2.const_tags[id(t)] = _ConstWord(t._version, t.data_ptr(), slot, weakref.ref(t))
     return slot
 
 
@@ -1049,7 +1107,7 @@ def _h2_amax(t):
         return None
     call("tris_amax_bits_f32", P(t), t.numel(), slot, _stream())
     try:
-        t._h2 = (_H2["step"], slot, t._version)
+        h2_tag(t, slot)
     except AttributeError:
         pass
     return slot
@@ -1074,7 +1132,7 @@ def h2_arm(A, B, a_slot=None, b_slot=None):
 # In h2 the activations of the RN50 trunk between a BatchNorm and the convolutions that read it, the gradients between a BatchNorm
 # backward and the convolution backward that reads it, and the convolution weights exist as fp16 PIECE PLANES: float32 tensors in
 # torch's eyes whose bytes are the two fp16 pieces of every element, scaled by the power of two their amax word implies.  The tensor
-# carries `_pl = (step, word)`; only the ops below that say so accept one, everything else must see `unplanes(t)`.
+# carries `_pl`, a _PlaneTag; only the ops below that say so accept one, everything else must see `unplanes(t)`.
 PL_STATS = {"unplanes": 0, "dx_planes": 0, "dy_planes": 0, "products": 0, "mixed": 0, "converted": 0}
 
 
@@ -1093,16 +1151,21 @@ def pl_word(t):
     tag = getattr(t, "_pl", None) if t is not None else None
     if tag is None:
         return None
-    if (tag[0] != _H2["step"] and tag[0] not in _H2.get("auto_pools", ())) or tag[2] != t.data_ptr():
+    if (tag.step != _H2.step and tag.step not in _H2.auto_pools) or tag.ptr != t.data_ptr():
         raise RuntimeError("a plane tensor outlived the step whose amax pool scales it")
-    return tag[1]
+    return tag.word
+
+
+def _pl_write(t, step, word, ptr):
+    """THE writer of t._pl, and of the amax tag that goes with it"""
+    t._pl = _PlaneTag(step, word, ptr)
+    h2_tag(t, word, step)
+    return t
 
 
 def pl_tag(t, word):
-    t._pl = (_H2["step"], word, t.data_ptr())
-    t._h2 = (_H2["step"], word, t._version)
-    _H2.setdefault("plane_numel", {})[word] = t.numel()
-    return t
+    _H2.plane_numel[word] = t.numel()
+    return _pl_write(t, _H2.step, word, t.data_ptr())
 
 
 def h2_range_report(threshold=0.01):
@@ -1111,8 +1174,7 @@ def h2_range_report(threshold=0.01):
     -> {"plane_tensors", "elements", "elements_below_floor", "max_fraction_below_floor", "out_of_range_operands"} where the last is the
     number of tensors with more than `threshold` of their elements in the absolute-accuracy regime (bench.py prints it as
     h2_out_of_range_operands; the B = 48 parity test asserts 0)."""
-    numel = _H2.get("plane_numel") or {}
-    pool = _H2["pool"]
+    numel, pool = _H2.plane_numel, _H2.pool
     if pool is None or not numel:
         return {"plane_tensors": 0, "elements": 0, "elements_below_floor": 0, "max_fraction_below_floor": 0.0, "out_of_range_operands": 0}
     torch.cuda.synchronize()
@@ -1131,7 +1193,7 @@ def _unplanes_raw(t, cache=True):
     if c is None:
         c = torch.empty_like(t)
         call("tris_h2_unplanes_f32", P(t), P(c), t.numel(), w, _stream())
-        c._h2 = (_H2["step"], w, c._version)   # (the word bounds the rebuilt values as well)
+        h2_tag(c, w)   # (the word bounds the rebuilt values as well)
         if cache:
             t._pl_f32 = c
         PL_STATS["unplanes"] += 1
@@ -1159,41 +1221,39 @@ def unplanes(t):
     return _unplanes_raw(t)
 
 
-_PL_CONST = {}   # id(parameter) -> (version, data_ptr, word, planes tensor, weakref): parameters outside the optimiser arenas
+_PL_CONST = {}   # id(parameter) -> _ConstPlanes: parameters outside the optimiser arenas
 
 
 def _pl_weight(w):
     """(pointer to the planes of a convolution weight, its amax word) or None"""
     tag = getattr(w, "_plw", None)
-    if tag is not None and tag[0] == _H2["step"]:
-        return tag[1], tag[2]
+    if tag is not None and tag.step == _H2.step:
+        return tag.ptr, tag.word
     if not _pl_weight_ok(w):
         return None
     word = _h2_amax(w)
     if word is None:
         return None
     c = _PL_CONST.get(id(w))
-    if c is not None and c[0] == w._version and c[1] == w.data_ptr() and c[2] == word and c[4]() is w:
-        return c[3].data_ptr(), word
-    import weakref
+    if _still_is(c, w) and c.version == w._version and c.word == word:
+        return c.planes.data_ptr(), word
     wc = cl_weight(w)
     pl = torch.empty(wc.numel(), device=w.device, dtype=torch.float32)
     call("tris_h2_planes_f32", wc.data_ptr(), P(pl), wc.numel(), word, _stream())
     if len(_PL_CONST) > 4096:
         _PL_CONST.clear()
-    _PL_CONST[id(w)] = (w._version, w.data_ptr(), word, pl, weakref.ref(w))
+    _PL_CONST[id(w)] = _ConstPlanes(w._version, w.data_ptr(), word, pl, weakref.ref(w))
     return pl.data_ptr(), word
 
 
 def _retag(t, tag):
     """a tensor that comes back from ctx.saved_tensors keeps its plane tag (set again in case autograd re-wrapped the object)"""
     if tag is not None and t is not None and getattr(t, "_pl", None) is None:
-        t._pl = tag
-        t._h2 = (tag[0], tag[1], t._version)
+        _pl_write(t, *tag)
     return t
 
 
-_PL_GRAD = {}   # data_ptr -> (step, word, shape): gradients a BatchNorm backward wrote as planes, until their one consumer takes them
+_PL_GRAD = {}   # data_ptr -> _PlaneGrad: gradients a BatchNorm backward wrote as planes, until their one consumer takes them
 
 
 _PL_GRAD_CB = [False]
@@ -1205,14 +1265,14 @@ def _pl_grad_end_of_backward():
     unrelated gradient that reuses the address.  Never silent: drop the entries and raise."""
     _PL_GRAD_CB[0] = False
     if _PL_GRAD:
-        left = [(hex(k), v[2]) for k, v in _PL_GRAD.items()]
+        left = [(hex(k), v.shape) for k, v in _PL_GRAD.items()]
         _PL_GRAD.clear()
         raise RuntimeError(f"plane gradients without a plane-aware consumer at the end of backward: {left[:4]}")
 
 
 def pl_grad_out(t, word):
     pl_tag(t, word)
-    _PL_GRAD[t.data_ptr()] = (_H2["step"], word, tuple(t.shape))
+    _PL_GRAD[t.data_ptr()] = _PlaneGrad(_H2.step, word, tuple(t.shape))
     PL_STATS["dx_planes"] += 1
     if not _PL_GRAD_CB[0]:
         try:   # (inside an autograd pass: BatchNormFn.backward calls this)
@@ -1227,10 +1287,9 @@ def pl_grad_in(dy):
     """the gradient a backward is handed: tag it as a plane tensor if a BatchNorm backward wrote it as one (one consumer: the entry
     is taken).  Returns dy."""
     ent = _PL_GRAD.pop(dy.data_ptr(), None)
-    if ent is not None and ent[0] == _H2["step"] and ent[2] == tuple(dy.shape):
+    if ent is not None and ent.step == _H2.step and ent.shape == tuple(dy.shape):
         if getattr(dy, "_pl", None) is None:
-            dy._pl = (ent[0], ent[1], dy.data_ptr())
-            dy._h2 = (ent[0], ent[1], dy._version)
+            _pl_write(dy, ent.step, ent.word, dy.data_ptr())
         PL_STATS["dy_planes"] += 1
     elif getattr(dy, "_pl", None) is not None:
         raise RuntimeError("a plane gradient reached a second consumer")
@@ -1261,8 +1320,8 @@ def h2_pp(A, B, a_slot=None, b_slot=None, y_planes=False, w_a=False, w_b=False, 
         b_t = False
         if w_bt and wb is None and pa is not None:
             tt = getattr(B, "_plwt", None)
-            if tt is not None and tt[0] == _H2["step"]:
-                pb, b_t = (tt[1], tt[2]), True
+            if tt is not None and tt.step == _H2.step:
+                pb, b_t = (tt.ptr, tt.word), True
         if pa is not None and pb is not None:
             call("tris_h2_next_planes", pa[1], pb[1], (1 if y_planes else 0) | (2 if b_t else 0) | (4 if y_mask else 0))
             PL_STATS["products"] += 1
@@ -2721,6 +2780,14 @@ def xattn_timed_out(collective=False):
     return hit
 
 
+def _xattn_arm(*six):
+    """h2: the next pixel-row launch runs on two fp16 pieces per operand, scaled by the amax words of its six operands (a pre-pass where none is left)"""
+    if h2_on() and cfg.xattn_h2:
+        words = [_h2_amax(t) for t in six]
+        if all(w is not None for w in words):
+            call("tris_xattn_amax_next", *words)
+
+
 class XAttnFn(torch.autograd.Function):
     """Fused bilateral cross attention (model/attn.py:117-128): forward = tris_xattn_fwd (two launches for the whole
     batch); backward = nine large single GEMMs on the saved probabilities + two softmax-backward kernels."""
@@ -2744,12 +2811,8 @@ class XAttnFn(torch.autograd.Function):
             if ws_bytes > 0:
                 ws = torch.empty(ws_bytes // 4 + 4, device=dev, dtype=torch.float32)
                 sync = _xattn_sync(dev, B)
-                if kind == "px" and h2_on() and cfg.xattn_h2:
-                    # h2: the products of the launch run on two fp16 pieces per operand, scaled by the amax words the producing
-                    # projections left behind (a pre-pass where there is none)
-                    words = [_h2_amax(t) for t in (Qv, Kv, Vv, Qt, Kt, Vt)]
-                    if all(w is not None for w in words):
-                        call("tris_xattn_amax_next", *words)
+                if kind == "px":
+                    _xattn_arm(Qv, Kv, Vv, Qt, Kt, Vt)
                 done = _timed(f"xattn_fwd_{kind}", 8.0 * B * Pp * N * C, lambda: _declinable(
                     f"tris_xattn_{kind}_fwd_f32", P(Qv), P(Kv), P(Vv), P(Qt), P(Kt), P(Vt), P(new_vis), P(new_lan), P(probs), B,
                     Pp, N, C, P(ws), ws.numel() * 4, sync.data_ptr(), _stream()))
@@ -2777,10 +2840,7 @@ class XAttnFn(torch.autograd.Function):
         sync = _xattn_sync(dev, B)
         dQv, dKv, dVv = (torch.empty(B, Pp, C, device=dev, dtype=torch.float32) for _ in range(3))
         dS = torch.empty(3, B * Pp, N, device=dev, dtype=torch.float32)
-        if h2_on() and cfg.xattn_h2:
-            words = [_h2_amax(t) for t in (d_vis, Vv, d_lan, Qt, Kt, Vt)]
-            if all(w is not None for w in words):
-                call("tris_xattn_amax_next", *words)
+        _xattn_arm(d_vis, Vv, d_lan, Qt, Kt, Vt)
         slots = [_h2_slot() if h2_on() else None for _ in range(3)]   # the launch leaves the amax words of its three outputs
         if not _timed("xattn_bwd_px", 10.0 * B * Pp * N * C, lambda: _declinable(
                 "tris_xattn_px_bwd_f32", P(d_vis), P(d_lan), P(Vv), P(Qt), P(Kt), P(Vt), P(probs), P(dQv), P(dKv), P(dVv), P(dS), B, Pp,
@@ -2788,7 +2848,7 @@ class XAttnFn(torch.autograd.Function):
             return None
         for t, slot in zip((dQv, dKv, dVv), slots):
             if slot is not None:
-                t._h2 = (_H2["step"], slot, t._version)
+                h2_tag(t, slot)
         BP = B * Pp
         new = lambda: torch.empty(N, C, device=dev, dtype=torch.float32)
         dVt = gemm(dS[2], d_vis, new(), N, C, BP, N, C, C, True, False)       # Av^T . d_vis
